@@ -15,6 +15,13 @@ Other configs (`--config`): c2 = the reference's 2-DoF scene (Newton, its defaul
 envs, sensors disabled; c4 = mobile base + 32-beam lidar + 640x480 depth camera, 2048 envs per GPU;
 c5 = arm + 8 free boxes, PGS 50 iterations, 8192 envs per GPU.
 
+A plain run sets up, warms up, times `--steps` bench steps and prints the result line (`value`, and
+`ms_per_step`: wall milliseconds per timed bench step).  `--full` adds what the headline figure does
+not need (the CPU baseline, `cpu_baseline` in the line); `--dump-outputs DIR` writes what the last
+timed step left -- rank 0's qpos, qvel, sensordata, the depth frames last rendered, the gathered
+observations -- as DIR/<name>.npy (float32; an output over 10 MB as a fixed seeded sample of its
+envs).  The synthetic inputs depend only on the arguments, so two builds compare output for output.
+
 Prints ONE JSON line on rank 0.  Launch: `python bench.py` (1 GPU); `python bench.py --gpus N`
 spawns N ranks itself (one process per GPU, before any GPU call); under torchrun
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`) each rank runs directly.
@@ -46,7 +53,13 @@ def parse():
     p.add_argument("--period", type=int, default=10, help="physics steps per controller period")
     p.add_argument("--envs", type=int, default=0, help="envs per GPU (0: the config's default)")
     p.add_argument("--scene", default=None, help="override the config's scene")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure what the headline figure does not need: the CPU "
+                        "baseline (the fp64 oracle on every host core; c1: on one), reported as cpu_baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one left (qpos, qvel, sensordata, the last "
+                        "depth frames; c1: the joint states) as DIR/<name>.npy, float32, <= 64 MB in all")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample duration")
     p.add_argument("--config", choices=["c1", "c2", "c3", "c3m", "c4", "c5"], default="c3",
                    help="c3: the BASELINE metric (default); c1: the reference scene, 1 env, through the plugin host "
@@ -115,6 +128,55 @@ def cpu_baseline(model, period: int, target_s: float):
             "cpu_model": cpu_model, "cpus_visible": visible, "cpu_quota": quota, "pinned": cores <= visible,
             "sample": f"{n_envs} envs x {steps} steps of the same scene and synthetic inputs, fp64 CPU restatement "
                       f"(oracle/oracle.c, not upstream MuJoCo), {cores} pinned pthreads on {cpu_model}, {secs:.1f} s"}
+
+
+# ------------------------------------------------------------------------------------------------ outputs
+DUMP_ARRAY_BYTES = 10 << 20   # per array; at most six arrays are written: < 64 MB in all
+
+
+def dump_rows(n_rows: int, row_bytes: int) -> np.ndarray:
+    """the rows of an [n_rows, ...] output that --dump-outputs keeps: all of them, or, for an array over
+    DUMP_ARRAY_BYTES, a fixed seeded sample in ascending order (the same rows in every run)"""
+    keep = max(1, DUMP_ARRAY_BYTES // max(1, row_bytes))
+    if keep >= n_rows:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(0).choice(n_rows, size=keep, replace=False))
+
+
+def dump_output(out_dir: str, name: str, a: np.ndarray) -> None:
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    assert a.nbytes <= DUMP_ARRAY_BYTES, (name, a.nbytes)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def ctrl_table_device(torch, synth, model, env_ids, n_periods: int, period: int, dev: str):
+    """synth.ctrl_table as an fp32 [n_periods, n_envs, nu] tensor in HBM.  A long table is built in
+    slices of periods on a few host threads (numpy's sin releases the GIL) and copied slice by slice,
+    so the host never holds more than a few fp64 slices; the values are those of one call."""
+    chunk = 256
+    if n_periods <= chunk:
+        return torch.from_numpy(synth.ctrl_table(model, env_ids, n_periods, period).astype(np.float32)).to(dev)
+    from concurrent.futures import ThreadPoolExecutor
+    table = torch.empty((n_periods, len(env_ids), model.nu), dtype=torch.float32, device=dev)
+    starts = list(range(0, n_periods, chunk))
+
+    def part(p0: int) -> np.ndarray:
+        return synth.ctrl_table(model, env_ids, min(chunk, n_periods - p0), period, p0 * period).astype(np.float32)
+
+    workers = max(1, min(8, host_cores()[0]))
+    with ThreadPoolExecutor(workers) as pool:
+        pending = []
+        for p0 in starts:   # at most 2 x workers slices in flight
+            pending.append((p0, pool.submit(part, p0)))
+            if len(pending) >= 2 * workers:
+                q0, f = pending.pop(0)
+                a = f.result()
+                table[q0:q0 + a.shape[0]].copy_(torch.from_numpy(a))
+        for q0, f in pending:
+            a = f.result()
+            table[q0:q0 + a.shape[0]].copy_(torch.from_numpy(a))
+    return table
 
 
 # ------------------------------------------------------------------------------------------------ evidence
@@ -224,6 +286,10 @@ def run_c1(args):
     elapsed = time.perf_counter() - t0
     q = np.array([s.state("joint1/position"), s.state("joint2/position")])
     assert np.all(np.isfinite(q))
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, "joint_position", q)
+        dump_output(args.dump_outputs, "joint_velocity",
+                    np.array([s.state("joint1/velocity"), s.state("joint2/velocity")]))
     # single physics steps, one per call (each a launch + synchronous state copy)
     n1 = max(50, args.steps)
     t1 = time.perf_counter()
@@ -251,7 +317,7 @@ def run_c1(args):
                      "note": "one env occupies one 16-lane group of one wave: a launch- and copy-latency "
                              "measurement, not a roofline one; host overhead per cycle = ms_per_step - kernel_ms"},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, str(ROOT / "oracle"))
         import binding
         cores, visible, quota, cpu_model = host_cores()
@@ -311,7 +377,7 @@ def main():
     n = args.envs or {"c2": 4096, "c3": 8192, "c3m": 8192, "c4": 2048, "c5": 8192}[cfg]
     env_ids = shard.env_ids(rank, n)
     P = args.warmup + args.steps
-    d_table = torch.from_numpy(synth.ctrl_table(model, env_ids, P, args.period).astype(np.float32)).to(dev)
+    d_table = ctrl_table_device(torch, synth, model, env_ids, P, args.period, dev)
 
     stream = torch.cuda.Stream(device=local)
     batch = sim.Batch(model, n, device=local)
@@ -397,6 +463,22 @@ def main():
     assert np.all(np.isfinite(q)), "non-finite state after benchmark"
     if render:
         assert torch.isfinite(frames).all(), "non-finite depth"
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: rank 0's env states and sensor
+        # readings (fp32 on the device), the depth frames last rendered, the rows gathered from all ranks
+        for name, field in (("qpos", sim.FIELD_QPOS), ("qvel", sim.FIELD_QVEL),
+                            ("sensordata", sim.FIELD_SENSORDATA)):
+            a = batch.get(field)
+            if a.shape[1]:
+                dump_output(args.dump_outputs, name, a[dump_rows(n, a.shape[1] * 4)])
+        if render:
+            rows = torch.from_numpy(dump_rows(n, W * H * 4)).to(dev)
+            dump_output(args.dump_outputs, "depth", frames[rows].cpu().numpy())
+        if gather is not None:
+            for name, g in zip(("gathered_qpos", "gathered_qvel"), gather.gathered(P - 1)):
+                g = g.reshape(world * n, -1)
+                rows = torch.from_numpy(dump_rows(world * n, g.shape[1] * 4)).to(dev)
+                dump_output(args.dump_outputs, name, g[rows].cpu().numpy())
 
     value = world * n * args.steps * args.period / elapsed
     solver = {0: "PGS", 1: "CG", 2: "Newton"}[model.solver]
@@ -479,7 +561,7 @@ def main():
     }
     if render:
         result["depth_frames_per_s"] = world * n * len(rend_list) / elapsed
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(model, args.period, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -16,10 +16,10 @@ if [ "${PART:-A}" = A ]; then
     [ $rc -ne 0 ] && exit $rc
     timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || exit $?
   fi
-  timeout -k 10 120 python bench.py --config c1 > gpurun_out/bench_c1.json 2> gpurun_out/bench_c1.err || exit $?
-  for v in $VARIANTS; do
+  # (c1, the plugin-host line, first; bench.py measures the CPU baseline only with --full)
+  for v in c1:c1: $VARIANTS; do
     key=${v%%:*}; rest=${v#*:}; cfg=${rest%%:*}; extra=$(echo ${rest#*:} | tr ',' ' ')
-    cpu=""; [ -n "$extra" ] && cpu="--no-cpu-baseline"
+    cpu="--full"; [ -n "$extra" ] && cpu=""
     timeout -k 10 300 python bench.py --config $cfg $extra $cpu > gpurun_out/bench_$key.json 2> gpurun_out/bench_$key.err || exit $?
   done
   exit 0
