@@ -1650,6 +1650,34 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
   }
   d.nrgeom = static_cast<int>(rgeom.size() / 8);
   P.addf(&d.rgeom, rgeom);
+  // eigenvector of the smallest eigenvalue of a symmetric 3 x 3 matrix (cyclic Jacobi): the normal of
+  // a fan of directions from their sum d d'
+  auto smallest_eigvec = [](const double cov[3][3], double c[3]) {
+    double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    std::memcpy(A, cov, sizeof A);
+    for (int sweep = 0; sweep < 50; ++sweep)
+      for (int p = 0; p < 2; ++p)
+        for (int q = p + 1; q < 3; ++q) {
+          if (std::abs(A[p][q]) < 1e-15) continue;
+          const double th = 0.5 * std::atan2(2 * A[p][q], A[q][q] - A[p][p]);
+          const double cs = std::cos(th), sn = std::sin(th);
+          for (int k = 0; k < 3; ++k) {
+            const double akp = A[k][p], akq = A[k][q];
+            A[k][p] = cs * akp - sn * akq; A[k][q] = sn * akp + cs * akq;
+          }
+          for (int k = 0; k < 3; ++k) {
+            const double apk = A[p][k], aqk = A[q][k];
+            A[p][k] = cs * apk - sn * aqk; A[q][k] = sn * apk + cs * aqk;
+          }
+          for (int k = 0; k < 3; ++k) {
+            const double vkp = V[k][p], vkq = V[k][q];
+            V[k][p] = cs * vkp - sn * vkq; V[k][q] = sn * vkp + cs * vkq;
+          }
+        }
+    int imin = 0;
+    for (int i = 1; i < 3; ++i) if (A[i][i] < A[imin][imin]) imin = i;
+    for (int i = 0; i < 3; ++i) c[i] = V[i][imin];
+  };
   // ray blocks (kRayBlock consecutive rangefinders) for the level-1 cull.  When every ray of a block
   // starts at the same point of the same body the block is bounded by a fan fixed in that body's
   // frame: unit axis a, in-plane direction b and normal c (the least-spread direction of the rays),
@@ -1685,30 +1713,7 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
       if (ok) {
         for (int i = 0; i < 3; ++i) axis[i] /= an;
         // normal of the fan: eigenvector of the smallest eigenvalue of sum d d' (cyclic Jacobi)
-        double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-        std::memcpy(A, cov, sizeof A);
-        for (int sweep = 0; sweep < 50; ++sweep)
-          for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-              if (std::abs(A[p][q]) < 1e-15) continue;
-              const double th = 0.5 * std::atan2(2 * A[p][q], A[q][q] - A[p][p]);
-              const double cs = std::cos(th), sn = std::sin(th);
-              for (int k = 0; k < 3; ++k) {
-                const double akp = A[k][p], akq = A[k][q];
-                A[k][p] = cs * akp - sn * akq; A[k][q] = sn * akp + cs * akq;
-              }
-              for (int k = 0; k < 3; ++k) {
-                const double apk = A[p][k], aqk = A[q][k];
-                A[p][k] = cs * apk - sn * aqk; A[q][k] = sn * apk + cs * aqk;
-              }
-              for (int k = 0; k < 3; ++k) {
-                const double vkp = V[k][p], vkq = V[k][q];
-                V[k][p] = cs * vkp - sn * vkq; V[k][q] = sn * vkp + cs * vkq;
-              }
-            }
-        int imin = 0;
-        for (int i = 1; i < 3; ++i) if (A[i][i] < A[imin][imin]) imin = i;
-        for (int i = 0; i < 3; ++i) c[i] = V[i][imin];
+        smallest_eigvec(cov, c);
         const double ca = c[0] * axis[0] + c[1] * axis[1] + c[2] * axis[2];
         for (int i = 0; i < 3; ++i) c[i] -= ca * axis[i];
         const double cn = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
@@ -2019,6 +2024,96 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
       }
     }
   }
+  // ray sweep (step.hip rays_sweep): a static lidar over a static world (rf_mode 2) whose rays are one
+  // planar, evenly spaced fan from one point -- what <replicate> builds -- and whose sensordata slots
+  // are consecutive.  Each step then computes, per moving ray geom, the interval of ray indices its
+  // bounding sphere can reach, copies the static hit of every ray in no interval and traces only the
+  // rows of G rays that meet one.  The fan is fitted in fp64 over all rays, as the block fit above
+  // does per block; ray k must lie within a quarter increment of phi0 + k dphi.  The helper-wave
+  // kernels keep the block passes.  MRS_NO_RAY_SWEEP=1 forces the block passes (A/B)
+  d.rf_sweep = 0;
+  if (d.rf_mode == 2 && d.rf_common && d.rf_static_frame && d.nrgeom <= 32 && (b.group == 16 || b.group == 32) &&
+      !b.helpers && d.nrf >= 3 && (d.nrf + b.group - 1) / b.group <= 32 && !std::getenv("MRS_NO_RAY_SWEEP")) {
+    bool ok = true;
+    for (int i = 0; i < d.nrgeom; ++i) {
+      int type;
+      std::memcpy(&type, &rgeom[8 * i + 1], 4);
+      if (!((d.rf_static_mask >> i) & 1u) && type == MRS_GEOM_MESH) ok = false;
+    }
+    const int adr0 = m.sensor_adr[rf[0]];
+    for (int k = 0; k < d.nrf; ++k) ok = ok && m.sensor_adr[rf[k]] == adr0 + k;
+    // (the directions the kernel traces: rfray, world frame)
+    auto dir = [&](int k, double v[3]) { for (int i = 0; i < 3; ++i) v[i] = rfray[8 * k + i]; };
+    double cov[3][3] = {}, c[3] = {0, 0, 1}, a[3], bv[3], d0[3];
+    for (int k = 0; k < d.nrf; ++k) {
+      double v[3];
+      dir(k, v);
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) cov[i][j] += v[i] * v[j];
+    }
+    smallest_eigvec(cov, c);
+    dir(0, d0);
+    const double cd = c[0] * d0[0] + c[1] * d0[1] + c[2] * d0[2];
+    for (int i = 0; i < 3; ++i) a[i] = d0[i] - cd * c[i];
+    const double an = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    const double cn = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    if (an < 0.5 || cn < 0.5) ok = false;
+    double dphi = 0, eps = 0;
+    if (ok) {
+      for (int i = 0; i < 3; ++i) { a[i] /= an; c[i] /= cn; }
+      auto cross_ca = [&]() {
+        bv[0] = c[1] * a[2] - c[2] * a[1];
+        bv[1] = c[2] * a[0] - c[0] * a[2];
+        bv[2] = c[0] * a[1] - c[1] * a[0];
+      };
+      cross_ca();
+      double d1[3];
+      dir(1, d1);
+      if (d1[0] * bv[0] + d1[1] * bv[1] + d1[2] * bv[2] < 0) {  // the sweep runs counter-clockwise about c
+        for (int i = 0; i < 3; ++i) c[i] = -c[i];
+        cross_ca();
+      }
+      // unwrapped in-plane angles (phi0 = 0: a is ray 0), each increment in (0, pi)
+      std::vector<double> phi(d.nrf, 0.0);
+      for (int k = 0; k < d.nrf; ++k) {
+        double v[3];
+        dir(k, v);
+        const double da = v[0] * a[0] + v[1] * a[1] + v[2] * a[2], db = v[0] * bv[0] + v[1] * bv[1] + v[2] * bv[2];
+        eps = std::max(eps, std::abs(v[0] * c[0] + v[1] * c[1] + v[2] * c[2]));
+        if (k == 0) continue;
+        const double kPi = 3.14159265358979323846;
+        double inc = std::atan2(db, da) - std::fmod(phi[k - 1], 2 * kPi);
+        while (inc <= 0) inc += 2 * kPi;
+        if (inc >= kPi) ok = false;
+        phi[k] = phi[k - 1] + inc;
+      }
+      const double kTwoPi = 6.28318530717958647692;
+      dphi = phi[d.nrf - 1] / (d.nrf - 1);
+      // (increments fine enough for fp32 angles to stay well inside the one-ray margin of the intervals)
+      if (!(dphi >= 5e-3) || dphi > 0.5 || eps > 1e-3) ok = false;
+      for (int k = 0; k < d.nrf && ok; ++k) ok = std::abs(phi[k] - k * dphi) <= 0.25 * dphi;
+      // no ray direction twice: the fan ends before ray 0 comes round again
+      if (ok && (d.nrf - 1) * dphi > kTwoPi - 0.5 * dphi) ok = false;
+      if (ok) {
+        d.rf_sw_full = std::abs(d.nrf * dphi - kTwoPi) <= 0.25 * dphi ? 1 : 0;
+        d.rf_sw_plo = static_cast<int>(std::floor(kTwoPi / dphi));
+        d.rf_sw_phi = static_cast<int>(std::ceil(kTwoPi / dphi));
+        d.rf_sw_n = d.nrf;
+        d.rf_sw_adr0 = adr0;
+        for (int i = 0; i < 3; ++i) {
+          d.rf_sw[i] = rfblk[2 + i];  // the origin every pass traces from (and level 1 tests against)
+          d.rf_sw[3 + i] = static_cast<float>(a[i]);
+          d.rf_sw[6 + i] = static_cast<float>(bv[i]);
+          d.rf_sw[9 + i] = static_cast<float>(c[i]);
+        }
+        d.rf_sw[12] = 0.0f;
+        d.rf_sw[13] = static_cast<float>(1.0 / dphi);
+        d.rf_sw[14] = static_cast<float>(eps + 1e-6);
+        d.rf_sw[15] = static_cast<float>(kTwoPi / dphi);
+        d.rf_sweep = 1;
+      }
+    }
+  }
   d.blocked = b.group == 64 ? 1 : 0;
   if (b.group == 64) d.shr_total = shr_small;
 
@@ -2139,6 +2234,7 @@ BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_cont
       // static ray hits: one forward-only pass of env 0 with the producer's model copy
       DevModel prod = b->dm;
       prod.rf_mode = 1;
+      prod.rf_sweep = 0;  // (the producer pass is a block pass over the static geoms)
       DevModel* d_prod = static_cast<DevModel*>(dalloc(*b, sizeof(DevModel)));
       HIP_CHECK(hipMemcpyAsync(d_prod, &prod, sizeof(DevModel), hipMemcpyHostToDevice, b->stream));
       HIP_CHECK(launch_step(d_prod, b->L.total, b->dm.shr_total, b->st, 1, 1, true, b->group, false, b->ext, b->stream));
@@ -2182,11 +2278,11 @@ void batch_free(BatchImpl* b) {
 int batch_num_envs(const BatchImpl* b) { return b->n; }
 
 int batch_layout(const BatchImpl* b, int* out, int n) {
-  const int v[14] = {b->group, b->dm.L.total, b->dm.S.total, b->dm.blocked, b->dm.pipe_w, b->dm.max_efc,
+  const int v[15] = {b->group, b->dm.L.total, b->dm.S.total, b->dm.blocked, b->dm.pipe_w, b->dm.max_efc,
                      b->dm.max_con, b->dm.ntree, b->dm.shr_total, b->dm.rf_common, b->g16_one_wg,
-                     b->group == 16 ? b->wpb16 : 0, b->helpers, b->dm.fuse_ih};
+                     b->group == 16 ? b->wpb16 : 0, b->helpers, b->dm.fuse_ih, b->dm.rf_sweep};
   int k = 0;
-  for (; k < n && k < 14; ++k) out[k] = v[k];
+  for (; k < n && k < 15; ++k) out[k] = v[k];
   return k;
 }
 

@@ -207,6 +207,14 @@ struct DevModel {
   // per rangefinder, 8 floats: unit direction[3], sensordata address (int bits), body (int bits),
   // origin[3], in the body frame
   CPtr<float> rfray;
+  // ray sweep: a static lidar whose rays are one planar, evenly spaced fan traces
+  // only the rows of rays (row = k / G) inside the index interval some moving geom's bounding sphere
+  // can reach; every other ray's value is its static hit.  rf_sw: origin o[3], in-plane a[3] (ray 0),
+  // b[3], normal c[3], phi0, 1 / dphi, out-of-plane slope eps, 2 pi / dphi (the period in rays);
+  // rf_sw_full: ray n would be ray 0 again (indices wrap); rf_sw_adr0: sensordata address of ray 0
+  // (consecutive); rf_sw_plo / _phi: floor / ceil of the period
+  int rf_sweep, rf_sw_n, rf_sw_full, rf_sw_adr0, rf_sw_plo, rf_sw_phi;
+  float rf_sw[16];
 };
 constexpr int kRayBlock = 128;
 

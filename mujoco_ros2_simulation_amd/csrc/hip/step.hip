@@ -6445,22 +6445,40 @@ struct RayBatch { static constexpr int value = G == 64 ? 2 : 4; };
 // site's +z over all visible geoms not on the site's body).  Each geom's pose is read from LDS once
 // for the R rays, and the R independent rays give the scheduler parallel work.  Rays k0 + j*stride.
 // kChunk: the pass covers ray geoms goff .. goff + 31 of a model with more than 32 (rays_chunked);
-// otherwise goff is 0 and the code is the <= 32-geom pass
-template <int G, int R, bool kChunk = false>
+// otherwise goff is 0 and the code is the <= 32-geom pass.
+// kSweep (rays_sweep; static lidar, common origin, no moving mesh): the rays are k0 + G * row for the
+// up to R lowest rows set in rowsel, and ray k is a candidate of ray geom i only inside the geom's
+// index interval -- lo in the low, hi - lo in the high half of lohi0 (i < G) / lohi1 of the group's
+// lane i % G; a full-circle fan (wrapn = ray count, else 0) wraps the indices
+template <int G, int R, bool kChunk = false, bool kSweep = false>
 __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se, gfloat* sd, int k0, int stride,
-                                             unsigned gmask, int common_body, const float* common_o, int goff_ = 0) {
+                                             unsigned gmask, int common_body, const float* common_o, int goff_ = 0,
+                                             unsigned rowsel = 0, int lohi0 = 0, int lohi1 = 0, int wrapn = 0) {
   const int goff = kChunk ? goff_ : 0;
   const LdsLayout& L = m.L;
   float pnt[R][3], vec[R][3], dist[R];
-  int bod[R], adr[R];
+  int bod[R], adr[R], krow[kSweep ? R : 1];
   bool act[R];
+  // (a sweep pass knows rf_mode 2, rf_common, rf_static_frame and the common origin, but reads them
+  // as the block passes do: the same selects between the same values keep the compiler's fused
+  // multiply-adds, and so every rounded bit of a hit, those of the block passes)
+  const int rf_mode = m.rf_mode, rf_common = m.rf_common, rf_static_frame = m.rf_static_frame;
+  if constexpr (kSweep) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      krow[j] = rowsel ? k0 + G * __builtin_ctz(rowsel) : m.nrf;
+      rowsel &= rowsel - 1;
+    }
+  }
+  auto ray_k = [&](int j) { return kSweep ? krow[kSweep ? j : 0] : k0 + j * stride; };
   unsigned long long t_setup = SUB_T();
-  if (common_body >= 0) {
+  const bool common = common_body >= 0;
+  if (common) {
     // every ray of the pass starts at the same point of the same body: one rotation for all (none
     // for a static lidar, whose rays are stored in the world frame)
     const int b = common_body;
     float bm[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, o[3] = {common_o[0], common_o[1], common_o[2]};
-    if (!m.rf_static_frame) {
+    if (!rf_static_frame) {
       float bq[4] = {se[L.xquat + 4 * b], se[L.xquat + 4 * b + 1], se[L.xquat + 4 * b + 2], se[L.xquat + 4 * b + 3]};
       quat2mat(bm, bq);
       mat_vec(o, bm, common_o);
@@ -6468,12 +6486,12 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
     }
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-      const int k = k0 + j * stride;
+      const int k = ray_k(j);
       act[j] = k < m.nrf;
       // the ray table is staged in workgroup LDS only when every ray shares body and origin
       // (rf_common); a pass that shares them in a model that does not reads the model block
       float dl[3];
-      if (m.rf_common) {
+      if (rf_common) {
         const lfloat* rr = shared_lds(m) + m.shr_rf + 4 * (act[j] ? k : 0);
         dl[0] = rr[0]; dl[1] = rr[1]; dl[2] = rr[2];
         adr[j] = __float_as_int(rr[3]);
@@ -6483,18 +6501,18 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
         adr[j] = __float_as_int(rr[3]);
       }
       bod[j] = b;
-      if (m.rf_static_frame) { vec[j][0] = dl[0]; vec[j][1] = dl[1]; vec[j][2] = dl[2]; }
+      if (rf_static_frame) { vec[j][0] = dl[0]; vec[j][1] = dl[1]; vec[j][2] = dl[2]; }
       else mat_vec(vec[j], bm, dl);
       for (int i = 0; i < 3; ++i) pnt[j][i] = o[i];
       // static split: start from the ray's hit on the world-welded geoms (never beaten: -1); later
       // chunks of ray geoms start from the earlier chunks' nearest hit in the output slot
-      dist[j] = m.rf_mode == 2 ? (float)shared_lds(m)[m.shr_rfst + (act[j] ? k : 0)] : -1.0f;
+      dist[j] = rf_mode == 2 ? (float)shared_lds(m)[m.shr_rfst + (act[j] ? k : 0)] : -1.0f;
       if (kChunk && goff > 0) dist[j] = act[j] && MRS_SD_OK(sd) ? (float)sd[adr[j]] : -1.0f;
     }
   } else {
 #pragma unroll
     for (int j = 0; j < R; ++j) {
-      const int k = k0 + j * stride;
+      const int k = ray_k(j);
       act[j] = k < m.nrf;
       const CPtr<float> rr = m.rfray + 8 * (act[j] ? k : 0);
       const float dl[3] = {rr[0], rr[1], rr[2]}, ol[3] = {rr[5], rr[6], rr[7]};
@@ -6511,7 +6529,7 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
         for (int i = 0; i < 3; ++i) pnt[j][i] += se[L.xpos + 3 * b + i];
         mat_vec(vec[j], bm, dl);
       }
-      dist[j] = m.rf_mode == 2 ? (float)shared_lds(m)[m.shr_rfst + (act[j] ? k : 0)] : -1.0f;
+      dist[j] = rf_mode == 2 ? (float)shared_lds(m)[m.shr_rfst + (act[j] ? k : 0)] : -1.0f;
       if (kChunk && goff > 0) dist[j] = act[j] && MRS_SD_OK(sd) ? (float)sd[adr[j]] : -1.0f;
     }
   }
@@ -6546,17 +6564,27 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
     // geom centre within rb, centre not behind the origin by more than rb, and no chance of beating
     // the current nearest hit; ray directions are unit (rotation-matrix columns)
     unsigned cmask = 0;
+    int ilo = 0, ilen = 0;
+    if constexpr (kSweep) {
+      const int lh = __float_as_int(gbcast<G>(__int_as_float(i < G ? lohi0 : lohi1), i & (G - 1)));
+      ilo = lh & 0xffff;
+      ilen = lh >> 16;
+    }
 #pragma unroll
     for (int j = 0; j < R; ++j) {
       const float dv[3] = {pnt[j][0] - gp[0], pnt[j][1] - gp[1], pnt[j][2] - gp[2]};
       const float tp = -dot3(dv, vec[j]);
       const float d2 = dot3(dv, dv) - tp * tp;
       const bool near = (d2 <= rb * rb) & (tp >= -rb) & ((dist[j] < 0) | (tp - rb <= dist[j]));
-      const bool c = gsel & act[j] & (gb != bod[j]) & ((type == MRS_GEOM_PLANE) | near);
+      bool c = gsel & act[j] & (gb != bod[j]) & ((type == MRS_GEOM_PLANE) | near);
+      if constexpr (kSweep) {
+        const int dk = ray_k(j) - ilo;  // (a ray below lo of a fan that does not wrap: huge as unsigned)
+        c &= static_cast<unsigned>(dk < 0 ? dk + wrapn : dk) <= static_cast<unsigned>(ilen);
+      }
       cmask |= static_cast<unsigned>(c) << j;
     }
     if (!__any(cmask != 0)) continue;
-    if (type == MRS_GEOM_MESH) {
+    if (!kSweep && type == MRS_GEOM_MESH) {
       // meshes are walked after the pass (below), when the pass's ray arrays are dead: record the
       // candidates (slot of R bits), or walk every ray past MaxSlots mesh geoms
       if (nms < kMaxSlots) {
@@ -6573,7 +6601,7 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
     const CPtr<float> gs = rec + 4;
     // rays of a pass from one origin: the origin goes into the geom frame once, not once per ray
     float lp0[3] = {0, 0, 0};
-    if (common_body >= 0) {
+    if (common) {
       const float dv[3] = {pnt[0][0] - gp[0], pnt[0][1] - gp[1], pnt[0][2] - gp[2]};
       matT_vec(lp0, gm, dv);
     }
@@ -6581,7 +6609,7 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
     for (int j = 0; j < R; ++j) {
       if (!((cmask >> j) & 1)) continue;
       float lp[3] = {lp0[0], lp0[1], lp0[2]}, lv[3];
-      if (common_body < 0) {
+      if (!common) {
         const float dv[3] = {pnt[j][0] - gp[0], pnt[j][1] - gp[1], pnt[j][2] - gp[2]};
         matT_vec(lp, gm, dv);
       }
@@ -6649,14 +6677,14 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
 #pragma unroll
     for (int j = 0; j < R; ++j) {
       if (m.rf_mode == 1) {
-        if (act[j]) m.rf_static[k0 + j * stride] = dist[j];
+        if (act[j]) m.rf_static[ray_k(j)] = dist[j];
       } else if (act[j] && sd_ok) {
         sd[adr[j]] = dist[j];
       }
     }
     // one walk: ray js of this lane against ray geom i (lane-varying)
     auto walk = [&](bool has, int i, int js) {
-      const int k = k0 + js * stride;
+      const int k = k0 + js * stride;  // (no mesh walk in a sweep pass)
       float p[3], v[3];
       const int rb = ray_of(k, p, v);
       const CPtr<float> rec = m.rgeom + 8 * (goff + i);
@@ -6709,8 +6737,8 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
   }
 #pragma unroll
   for (int j = 0; j < R; ++j) {
-    if (m.rf_mode == 1) {
-      if (act[j]) m.rf_static[k0 + j * stride] = dist[j];  // producer pass: the static hits
+    if (rf_mode == 1) {
+      if (act[j]) m.rf_static[ray_k(j)] = dist[j];  // producer pass: the static hits
     } else if (act[j] && MRS_SD_OK(sd)) {
 #ifdef MRS_DIAG_SD_SINK
       asm volatile("" ::"v"(dist[j]));  // diagnostic build: the ray result is kept live, not stored
@@ -6741,6 +6769,143 @@ __device__ void rays_chunked(ENV_PARAMS, gfloat* sensordata) {
   }
 }
 
+// the sweep code is left out of the helper-wave kernels' translation unit (they keep the block passes;
+// batch.hip never sets rf_sweep with helper waves)
+#if defined(MRS_STEP_PART) && MRS_STEP_PART == 19
+constexpr bool kRaySweepBuilt = false;
+#else
+constexpr bool kRaySweepBuilt = true;
+#endif
+#ifndef MRS_SWEEP_ROWS
+#define MRS_SWEEP_ROWS 4
+#endif
+
+// The rangefinders of a static planar lidar with evenly spaced rays (DevModel::rf_sweep): instead of
+// testing every block of rays against every geom, each moving ray geom gives the interval of ray
+// indices its bounding sphere can reach, and only the rows of G rays (ray k: row k / G, lane k % G)
+// that meet an interval of some group of the wave are traced; every other ray gets its static hit.
+// A traced ray runs the block passes' cull and intersection on the same inputs, and the minimum over
+// geoms does not depend on their order, so the values are those of the block passes.
+template <int G>
+__device__ __forceinline__ void rays_sweep(ENV_PARAMS, gfloat* sensordata) {
+  ENV_UNPACK;
+  const int n = m.rf_sw_n;
+  const float o[3] = {m.rf_sw[0], m.rf_sw[1], m.rf_sw[2]};
+  unsigned gmask = 0, rows = 0;
+  int lohi0 = 0, lohi1 = 0;
+  {
+    // intervals: lanes over the moving ray geoms.  Out of plane as level 1 rejects (rr); in plane the
+    // centre's angle +- asin(rb / |w|) with level 1's inflated rb, in ray indices, rounded outwards
+    // and widened by a ray on each side (the rays lie within a quarter increment of their slots)
+    const float a[3] = {m.rf_sw[3], m.rf_sw[4], m.rf_sw[5]}, bb[3] = {m.rf_sw[6], m.rf_sw[7], m.rf_sw[8]};
+    const float c[3] = {m.rf_sw[9], m.rf_sw[10], m.rf_sw[11]};
+    const float phi0 = m.rf_sw[12], inv_dphi = m.rf_sw[13], eps = m.rf_sw[14];
+    const unsigned moving = ~m.rf_static_mask;
+    #pragma unroll 1
+    for (int c0 = 0; c0 < m.nrgeom; c0 += G) {
+      const int i = c0 + lane;
+      bool cand = false;
+      int lo = 0, len = n - 1;  // (all rays)
+      if (i < m.nrgeom && ((moving >> i) & 1u)) {
+        const lfloat* rec = shared_lds(m) + 8 * i;
+        const int g = __float_as_int(rec[0]), type = __float_as_int(rec[1]);
+        const float v[3] = {s[L.gxpos + 3 * g] - o[0], s[L.gxpos + 3 * g + 1] - o[1], s[L.gxpos + 3 * g + 2] - o[2]};
+        const float rb = rec[3] * 1.0001f + 1e-6f;
+        const float l2 = dot3(v, v);
+        const float rr = rb + eps * (sqrtf(l2) + rb);
+        const float wa = dot3(v, a), wb = dot3(v, bb), h = dot3(v, c);
+        const float wn2 = wa * wa + wb * wb;
+        const float rbi = rb * 1.001f + 1e-4f;
+        if (type == MRS_GEOM_PLANE || l2 <= rb * rb) {
+          cand = true;
+        } else if (fabsf(h) <= rr) {
+          cand = true;
+          const float tc = (atan2f(wb, wa) - phi0) * inv_dphi;
+          // (a centre too far off for fp32 to give an angle: every ray)
+          if (wn2 > rbi * rbi && fabsf(tc) <= m.rf_sw[15]) {
+            const float dt = asinf(rbi * rsqrtf(wn2)) * inv_dphi;
+            const int l0 = static_cast<int>(floorf(tc - dt)) - 1, h0 = static_cast<int>(ceilf(tc + dt)) + 1;
+            if (m.rf_sw_full) {
+              if (h0 - l0 + 1 < n) {
+                lo = l0 < 0 ? l0 + n : (l0 >= n ? l0 - n : l0);
+                len = h0 - l0;
+              }
+            } else {
+              // the interval and its image one turn on, clamped to the fan: none, one, or (a fan of
+              // almost a full turn) both -- then every ray
+              const int la = max(l0, 0), ha = min(h0, n - 1);
+              const int lb = max(l0 + m.rf_sw_plo, 0), hb = min(h0 + m.rf_sw_phi, n - 1);
+              if (la > ha && lb > hb) cand = false;
+              else if (lb > hb) { lo = la; len = ha - la; }
+              else if (la > ha) { lo = lb; len = hb - lb; }
+            }
+          }
+        }
+      }
+      if (cand) {
+        // rows of the interval; past the last ray it continues at ray 0 (full circle only)
+        const int r0 = lo / G, e = lo + len;
+        const int r1 = min(e, n - 1) / G;
+        rows |= (0xffffffffu >> (31 - r1)) & (0xffffffffu << r0);
+        if (e >= n) rows |= 0xffffffffu >> (31 - (e - n) / G);
+      }
+      const int lh = lo | (len << 16);
+      if (c0 == 0) lohi0 = lh;
+      else lohi1 = lh;
+      const unsigned long long bal = __ballot(cand);
+      const unsigned bits = static_cast<unsigned>((bal >> (__lane_id() & ~(G - 1))) & ((1ull << G) - 1));
+      gmask |= c0 < 32 ? bits << c0 : 0u;
+    }
+  }
+  // the wave's rows: OR over each row of 16 lanes (DPP), then over the four rows
+  {
+    float r = __int_as_float(static_cast<int>(rows));
+    auto ior = [](float x, float y) { return __int_as_float(__float_as_int(x) | __float_as_int(y)); };
+    r = ior(r, dpp<kDppXor1>(r));
+    r = ior(r, dpp<kDppXor2>(r));
+    r = ior(r, dpp<kDppHalfMirror>(r));
+    r = ior(r, dpp<kDppMirror>(r));
+    const int ri = __float_as_int(r);
+    rows = static_cast<unsigned>(__builtin_amdgcn_readlane(ri, 0) | __builtin_amdgcn_readlane(ri, 16) |
+                                 __builtin_amdgcn_readlane(ri, 32) | __builtin_amdgcn_readlane(ri, 48));
+  }
+#ifdef MRS_SWEEP_STATS
+  if (__lane_id() == 0) {
+    // counting build (with MRS_PHASE_TIMING): rows traced and wave-steps, in two slots only the blocked
+    // solver uses
+    atomicAdd(&g_phase_cycles[PH_REC_ROWS], static_cast<unsigned long long>(__popc(rows)));
+    atomicAdd(&g_phase_cycles[PH_REC_SOLVE], 1ull);
+  }
+#endif
+  // rows no group of the wave can reach: the static hits, four rows in flight
+  const int nrows = (n + G - 1) / G;
+  unsigned cold = ~rows & (0xffffffffu >> (32 - nrows));
+  const lfloat* stat = shared_lds(m) + m.shr_rfst;
+  gfloat* out = sensordata + m.rf_sw_adr0;
+  #pragma unroll 1
+  while (cold) {
+    float v[4];
+    int k[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      k[j] = cold ? lane + G * __builtin_ctz(cold) : n;
+      cold &= cold - 1;
+      v[j] = stat[k[j] < n ? k[j] : 0];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (k[j] < n && MRS_SD_OK(sensordata)) out[k[j]] = v[j];
+  }
+  // the other rows: the block passes' geom loop, MRS_SWEEP_ROWS rows per call
+  #pragma unroll 1
+  while (rows) {
+    rangefinders<G, MRS_SWEEP_ROWS, false, true>(m, s, sensordata, lane, G, gmask, __float_as_int(shared_lds(m)[m.shr_blk]),
+                                                 o, 0, rows, lohi0, lohi1, m.rf_sw_full ? n : 0);
+#pragma unroll
+    for (int j = 0; j < MRS_SWEEP_ROWS; ++j) rows &= rows - 1;
+  }
+}
+
 // mj_sensorPos/Vel for the implemented sensor types; rangefinders lane-parallel within the group,
 // RayBatch<G> rays per lane per pass
 template <int G>
@@ -6748,6 +6913,12 @@ __device__ __forceinline__ void rays_pass(ENV_PARAMS, gfloat* sensordata) {
   ENV_UNPACK;
   if constexpr (G == 64) sensordata = uniform_ptr(sensordata);
   if (m.disableflags & MRS_DSBL_SENSOR) return;
+  if constexpr (kRaySweepBuilt && (G == 16 || G == 32)) {
+    if (m.rf_sweep) {
+      rays_sweep<G>(ENV_ARGS, sensordata);
+      return;
+    }
+  }
   // level 1: which ray geoms can a ray block reach at all (fan bound of the block vs bounding sphere
   // of the geom; planes by the direction range of the fan), one bitmask per block; lanes over geoms
   const unsigned all = m.nrgeom >= 32 ? 0xffffffffu : ((1u << m.nrgeom) - 1u);
