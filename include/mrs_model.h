@@ -45,7 +45,11 @@ enum { MRS_OBJ_UNKNOWN = 0, MRS_OBJ_BODY = 1, MRS_OBJ_JOINT = 3, MRS_OBJ_GEOM = 
        MRS_OBJ_CAMERA = 7, MRS_OBJ_MESH = 10, MRS_OBJ_TENDON = 18, MRS_OBJ_ACTUATOR = 19, MRS_OBJ_SENSOR = 20 };
 enum { MRS_SENS_ACCELEROMETER = 1, MRS_SENS_GYRO = 3, MRS_SENS_FORCE = 4, MRS_SENS_TORQUE = 5,
        MRS_SENS_RANGEFINDER = 7, MRS_SENS_JOINTPOS = 9, MRS_SENS_JOINTVEL = 10,
-       MRS_SENS_ACTUATORFRC = 15, MRS_SENS_FRAMEPOS = 25, MRS_SENS_FRAMEQUAT = 26 };
+       MRS_SENS_ACTUATORFRC = 15, MRS_SENS_FRAMEPOS = 25, MRS_SENS_FRAMEQUAT = 26,
+       /* [upstream; verify] mjtSensor of MuJoCo 3.3.4 */
+       MRS_SENS_TOUCH = 0, MRS_SENS_VELOCIMETER = 2, MRS_SENS_FRAMEXAXIS = 27, MRS_SENS_FRAMEYAXIS = 28,
+       MRS_SENS_FRAMEZAXIS = 29, MRS_SENS_FRAMELINVEL = 30, MRS_SENS_FRAMEANGVEL = 31,
+       MRS_SENS_FRAMELINACC = 32, MRS_SENS_SUBTREECOM = 34, MRS_SENS_SUBTREELINVEL = 35 };
 /* restate bits (not MuJoCo options; mrs_model_set_restate): opt-in variants of this restatement that
  * upstream does not have.  NEWTON_REFINE: after a Newton step that kept every row's state, one more
  * step from freshly formed residuals with the same factor, then stop (mj_solNewton instead keeps
@@ -195,6 +199,11 @@ typedef struct mrs_model_view {
   int nmeshpoly, nmeshpolyvert;
   const int *mesh_polyadr, *mesh_polynum, *mesh_polyvertadr, *mesh_polyvertnum, *mesh_polyvert;
   const double *mesh_polynormal /*3*/;
+
+  /* site shapes (mjModel site_type / site_size; MRS_GEOM_* sphere, capsule, ellipsoid, cylinder or
+   * box): the zone of a touch sensor */
+  const int *site_type;
+  const double *site_size /*3*/;
 } mrs_model_view;
 
 #ifdef __cplusplus

@@ -1081,6 +1081,8 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
     int t = m.sensor_type[s];
     if (t == MRS_SENS_ACCELEROMETER) d.acc_sens |= 1;
     if (t == MRS_SENS_FORCE || t == MRS_SENS_TORQUE) d.acc_sens |= 3;
+    if (t == MRS_SENS_FRAMELINACC) d.acc_sens |= 1;  // reads cacc
+    if (t == MRS_SENS_TOUCH) d.acc_sens |= 2;        // reads the row forces
   }
   d.nq = m.nq; d.nv = m.nv; d.nu = m.nu; d.nbody = m.nbody; d.njnt = m.njnt; d.ngeom = m.ngeom;
   d.nsite = m.nsite; d.ncam = m.ncam; d.nsensor = m.nsensor; d.nsensordata = m.nsensordata;
@@ -1290,12 +1292,20 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
   for (int j = 0; j < m.nv; ++j) if (m.dof_frictionloss[j] > 0) fric.push_back(j);
   for (int j = 0; j < m.njnt; ++j)
     if (m.jnt_limited[j] && (m.jnt_type[j] == MRS_JNT_HINGE || m.jnt_type[j] == MRS_JNT_SLIDE)) lim.push_back(j);
-  std::vector<int> other_sens;
+  // sensors by kernel path: rangefinders (the ray passes), the velocity / axis / subtree / touch types
+  // (step.hip sensors_more, entered only by models that have one), the others (step.hip sensors)
+  auto sens_more = [](int t) {
+    return t == MRS_SENS_TOUCH || t == MRS_SENS_VELOCIMETER || t == MRS_SENS_SUBTREECOM || t == MRS_SENS_SUBTREELINVEL ||
+           (t >= MRS_SENS_FRAMEXAXIS && t <= MRS_SENS_FRAMELINACC);
+  };
+  std::vector<int> other_sens, more_sens;
   for (int s = 0; s < m.nsensor; ++s) {
     if (m.sensor_type[s] == MRS_SENS_RANGEFINDER) rf.push_back(s);
+    else if (sens_more(m.sensor_type[s])) more_sens.push_back(s);
     else other_sens.push_back(s);
   }
   d.nsens_other = static_cast<int>(other_sens.size());
+  d.nsens_more = static_cast<int>(more_sens.size());
   d.nfric = static_cast<int>(fric.size());
   d.nlim = static_cast<int>(lim.size());
   d.nrf = static_cast<int>(rf.size());
@@ -1637,6 +1647,34 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
                                      static_cast<float>(lq[0]), static_cast<float>(lq[1]), static_cast<float>(lq[2]),
                                      static_cast<float>(lq[3]), fbits(id), 0.0f});
     }
+    // then the records of sensors_more's types, 32 floats each: the same first 15 (the body and the
+    // local pose of the site / geom / body frame; the body's tree root), 15: one past the last body of
+    // the body's subtree (bodies of a subtree are contiguous), 16: the site's shape type (int bits),
+    // 17-19: its size, 20: the subtree's mass
+    for (int sid : more_sens) {
+      const int t = m.sensor_type[sid], ot = m.sensor_objtype[sid], id = m.sensor_objid[sid];
+      int a = id, st = MRS_GEOM_SPHERE;
+      double lp[3] = {0, 0, 0}, lq[4] = {1, 0, 0, 0}, sz[3] = {0, 0, 0};
+      if (ot == MRS_OBJ_SITE) {
+        a = m.site_bodyid[id];
+        for (int i = 0; i < 3; ++i) lp[i] = m.site_pos[3 * id + i];
+        for (int i = 0; i < 4; ++i) lq[i] = m.site_quat[4 * id + i];
+        for (int i = 0; i < 3; ++i) sz[i] = m.site_size[3 * id + i];
+        st = m.site_type[id];
+      } else if (ot == MRS_OBJ_GEOM) {
+        a = m.geom_bodyid[id];
+        for (int i = 0; i < 3; ++i) lp[i] = m.geom_pos[3 * id + i];
+        for (int i = 0; i < 4; ++i) lq[i] = m.geom_quat[4 * id + i];
+      }
+      sensrec.insert(sensrec.end(), {fbits(t), fbits(ot), fbits(m.sensor_adr[sid]), fbits(m.sensor_dim[sid]),
+                                     static_cast<float>(m.sensor_cutoff[sid]), fbits(a), fbits(m.body_rootid[a]),
+                                     static_cast<float>(lp[0]), static_cast<float>(lp[1]), static_cast<float>(lp[2]),
+                                     static_cast<float>(lq[0]), static_cast<float>(lq[1]), static_cast<float>(lq[2]),
+                                     static_cast<float>(lq[3]), fbits(id), fbits(a == 0 ? m.nbody : subtree_end[a]),
+                                     fbits(st), static_cast<float>(sz[0]), static_cast<float>(sz[1]),
+                                     static_cast<float>(sz[2]), static_cast<float>(m.body_subtreemass[a]),
+                                     0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f});
+    }
   }
   P.addf(&d.sensrec, sensrec);
   std::vector<float> rgeom;
@@ -1899,7 +1937,7 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
     d.shr_rfst = d.shr_rf + (d.rf_common ? 4 * d.nrf : 0);
     d.shr_blk = d.shr_rfst + (d.rf_mode == 2 ? d.nrf : 0);
     d.shr_sens = d.shr_blk + 17 * d.nrfblk;
-    d.shr_fric = d.shr_sens + 16 * d.nsens_other;
+    d.shr_fric = d.shr_sens + 16 * d.nsens_other + 32 * d.nsens_more;
     d.shr_lim = d.shr_fric + 4 * d.nfric;
     d.shr_act = d.shr_lim + 4 * d.nlim;
     d.shr_dof = d.shr_act + 20 * m.nu;

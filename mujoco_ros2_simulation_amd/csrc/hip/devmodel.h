@@ -103,7 +103,7 @@ struct DevModel {
   // in the world frame (batch.hip), and the kernel uses them without the per-step body rotation
   int rf_static_frame;
   // the ray blocks' level-1 records (rfblk, 16 floats each, then the nrfblk slopes) at shr_blk, the
-  // non-ray sensors' descriptors (sensrec, 16 floats each) at shr_sens
+  // non-ray sensors' descriptors (sensrec, 16 floats each, then sensors_more's 32 each) at shr_sens
   int shr_blk, shr_sens;
   // friction-loss rows (fricrec: dof, R, B, frictionloss) at shr_fric, limited joints (limrec: qpos
   // address, margin, range) at shr_lim
@@ -123,7 +123,8 @@ struct DevModel {
   int integrator, iterations, disableflags, solver, ls_iterations;
   int restate;  // MRS_RESTATE_* (mrs_model.h): opt-in solver variants, 0 = upstream rules
   int cone;  // MRS_CONE_*: elliptic models take the dense row path (3-row contact blocks)
-  int acc_sens;   // bit 0: accelerometer, bit 1: force/torque sensors present (mj_rnePostConstraint)
+  int acc_sens;   // bit 0: accelerometer / framelinacc (cacc), bit 1: force / torque / touch sensors (the row
+                  // forces) present (mj_rnePostConstraint)
   int diag_skip;  // profiling ablation only (MRS_DIAG_SKIP); 0 in every measured/parity run
   float timestep, tolerance, pgs_scale, gravity[3], impratio, ls_tolerance;
   double timestep_d;  // time is accumulated in fp64 like mjData.time
@@ -192,6 +193,9 @@ struct DevModel {
   CPtr<float> sensor_cutoff;
   CPtr<int> fric_dof, lim_jnt, rf_sensor, sens_other;  // sens_other: non-rangefinder sensor ids
   CPtr<float> sensrec;  // their descriptors (batch.hip), 16 floats each
+  // velocimeter, frame velocity / acceleration / axis, subtree and touch sensors (step.hip sensors_more):
+  // their count; their descriptors, 32 floats each, follow the others' in sensrec and at shr_sens
+  int nsens_more;
   CPtr<float> fricrec, limrec;  // 4 floats per friction-loss dof / limited joint (batch.hip)
   CPtr<float> actrec, dofrec;   // smooth-force tables (batch.hip)
   CPtr<float> bodytab, mpairtab;  // tree tables of the smooth dynamics (batch.hip)

@@ -7179,6 +7179,119 @@ __device__ MRS_PHASE void sensors(ENV_PARAMS, gfloat* sensordata, bool rays = tr
   }
 }
 
+// velocimeter, framelinvel / frameangvel / framelinacc, frame{x,y,z}axis, subtreecom / subtreelinvel and
+// touch sensors, one per lane like sensors().  Out of line and entered only by models that have one
+// (DevModel::nsens_more), so the kernels of every other model keep their registers; the descriptors are
+// the 32-float records behind sensors()'s in workgroup LDS (batch.hip sensrec).  Velocities and
+// accelerations are the body's cvel / cacc (about its tree's com) moved to the object's origin
+// (mj_objectVelocity / mj_objectAcceleration); the subtree values sum over the subtree's contiguous
+// bodies; touch sums the normal forces of the site body's contacts whose normal ray meets the site's
+// shape (mj_sensorAcc).  Needs rne_post's cacc (framelinacc) and this step's row forces (touch).
+template <int G>
+__device__ void sensors_more(ENV_PARAMS, gfloat* sensordata, int ncon) {
+  ENV_UNPACK;
+  if constexpr (G == 64) sensordata = uniform_ptr(sensordata);
+  #pragma unroll 1
+  for (int ks = lane; ks < m.nsens_more; ks += G) {
+    const lfloat* sr = shared_lds(m) + m.shr_sens + 16 * m.nsens_other + 32 * ks;
+    const int t = __float_as_int(sr[0]), b = __float_as_int(sr[5]), rt = __float_as_int(sr[6]);
+    gfloat* out = sensordata + __float_as_int(sr[2]);
+    float cutoff = sr[4];
+    float o0 = 0, o1 = 0, o2 = 0;
+    if (t == MRS_SENS_SUBTREECOM || t == MRS_SENS_SUBTREELINVEL) {
+      const int e = __float_as_int(sr[15]);
+      const float sm = sr[20];
+      const bool vel = t == MRS_SENS_SUBTREELINVEL;
+      #pragma unroll 1
+      for (int k = b; k < e; ++k) {
+        const float mk = m.body_mass[k];
+        float x0 = s[L.xipos + 3 * k], x1 = s[L.xipos + 3 * k + 1], x2 = s[L.xipos + 3 * k + 2];
+        if (vel) {
+          // the body com's velocity: cvel moved from the tree's com to xipos
+          const int rk = m.body_rootid[k];
+          const float d[3] = {x0 - s[L.scom + 3 * rk], x1 - s[L.scom + 3 * rk + 1], x2 - s[L.scom + 3 * rk + 2]};
+          const float w[3] = {s[L.cvel + 6 * k], s[L.cvel + 6 * k + 1], s[L.cvel + 6 * k + 2]};
+          float wd[3];
+          cross3(wd, w, d);
+          x0 = s[L.cvel + 6 * k + 3] + wd[0]; x1 = s[L.cvel + 6 * k + 4] + wd[1]; x2 = s[L.cvel + 6 * k + 5] + wd[2];
+        }
+        o0 += mk * x0; o1 += mk * x1; o2 += mk * x2;
+      }
+      if (sm > kMinVal) { const float im = 1.0f / sm; o0 *= im; o1 *= im; o2 *= im; }
+      else if (!vel) { o0 = s[L.xipos + 3 * b]; o1 = s[L.xipos + 3 * b + 1]; o2 = s[L.xipos + 3 * b + 2]; }
+    } else {
+      // the object's world pose from its body's
+      const float bq[4] = {s[L.xquat + 4 * b], s[L.xquat + 4 * b + 1], s[L.xquat + 4 * b + 2], s[L.xquat + 4 * b + 3]};
+      const float lp[3] = {sr[7], sr[8], sr[9]};
+      const float lq[4] = {sr[10], sr[11], sr[12], sr[13]};
+      float r[3], q[4], xm[9];
+      rot_quat(r, lp, bq);
+      const float p[3] = {s[L.xpos + 3 * b] + r[0], s[L.xpos + 3 * b + 1] + r[1], s[L.xpos + 3 * b + 2] + r[2]};
+      quat_mul(q, bq, lq);
+      quat_normalize(q);
+      quat2mat(xm, q);
+      if (t == MRS_SENS_TOUCH) {
+        const int stype = __float_as_int(sr[16]);
+        const float ssz[3] = {sr[17], sr[18], sr[19]};
+        const gfloat* ff = scr + S.efc_f;
+        #pragma unroll 1
+        for (int c = 0; c < ncon; ++c) {
+          const gfloat* rec = scr + S.con + kConRec * c;
+          const int pr = __float_as_int(rec[0]);
+          const int b1 = m.geom_bodyid[m.pair_g1[pr]], b2 = m.geom_bodyid[m.pair_g2[pr]];
+          const int r0 = __float_as_int(rec[14]);
+          if ((b != b1 && b != b2) || r0 < 0) continue;
+          // the contact's normal force (mj_contactForce): the edge forces' sum / the first row's force
+          float fn = ff[r0];
+          if (m.pair_dim[pr] != 1 && m.cone != MRS_CONE_ELLIPTIC) fn += ff[r0 + 1] + ff[r0 + 2] + ff[r0 + 3];
+          if (fn <= 0) continue;
+          // ray from the contact point along the normal (reversed when the site's body is the second)
+          const float sg = b == b2 ? -1.0f : 1.0f;
+          const float dv[3] = {rec[2] - p[0], rec[3] - p[1], rec[4] - p[2]};
+          const float nv[3] = {sg * rec[5], sg * rec[6], sg * rec[7]};
+          float rp[3], rv[3];
+          matT_vec(rp, xm, dv);
+          matT_vec(rv, xm, nv);
+          float hit;
+          [[clang::always_inline]] hit = ray_geom_local(stype, ssz, rp, rv);
+          if (hit >= 0) o0 += fn;
+        }
+        // (positive data type: the cutoff only caps it)
+        if (cutoff > 0 && o0 > cutoff) o0 = cutoff;
+        out[0] = o0;
+        continue;
+      }
+      if (t == MRS_SENS_FRAMEXAXIS) { o0 = xm[0]; o1 = xm[3]; o2 = xm[6]; cutoff = 0; }
+      else if (t == MRS_SENS_FRAMEYAXIS) { o0 = xm[1]; o1 = xm[4]; o2 = xm[7]; cutoff = 0; }
+      else if (t == MRS_SENS_FRAMEZAXIS) { o0 = xm[2]; o1 = xm[5]; o2 = xm[8]; cutoff = 0; }
+      else {
+        const float d[3] = {p[0] - s[L.scom + 3 * rt], p[1] - s[L.scom + 3 * rt + 1], p[2] - s[L.scom + 3 * rt + 2]};
+        const float w[3] = {s[L.cvel + 6 * b], s[L.cvel + 6 * b + 1], s[L.cvel + 6 * b + 2]};
+        float wd[3];
+        cross3(wd, w, d);
+        const float v[3] = {s[L.cvel + 6 * b + 3] + wd[0], s[L.cvel + 6 * b + 4] + wd[1], s[L.cvel + 6 * b + 5] + wd[2]};
+        if (t == MRS_SENS_FRAMEANGVEL) { o0 = w[0]; o1 = w[1]; o2 = w[2]; }
+        else if (t == MRS_SENS_FRAMELINVEL) { o0 = v[0]; o1 = v[1]; o2 = v[2]; }
+        else if (t == MRS_SENS_VELOCIMETER) {
+          float lv[3];
+          matT_vec(lv, xm, v);
+          o0 = lv[0]; o1 = lv[1]; o2 = lv[2];
+        } else {  // MRS_SENS_FRAMELINACC: a_lin + a_ang x d + w x v (the accelerometer's value, world frame)
+          const float aa[3] = {s[L.cacc + 6 * b], s[L.cacc + 6 * b + 1], s[L.cacc + 6 * b + 2]};
+          float ad[3], wv[3];
+          cross3(ad, aa, d);
+          cross3(wv, w, v);
+          o0 = s[L.cacc + 6 * b + 3] + ad[0] + wv[0];
+          o1 = s[L.cacc + 6 * b + 4] + ad[1] + wv[1];
+          o2 = s[L.cacc + 6 * b + 5] + ad[2] + wv[2];
+        }
+      }
+    }
+    if (cutoff > 0) { o0 = clampf(o0, -cutoff, cutoff); o1 = clampf(o1, -cutoff, cutoff); o2 = clampf(o2, -cutoff, cutoff); }
+    out[0] = o0; out[1] = o1; out[2] = o2;
+  }
+}
+
 // reset one env (mj_resetData; held inputs ctrl/qfrc_applied are re-applied by the caller's loop)
 template <int G>
 __device__ MRS_PHASE void reset_env(ENV_PARAMS) {
@@ -7272,6 +7385,7 @@ __device__ MRS_PHASE int forward(ENV_PARAMS, gfloat* sensordata PH_ACC_PARAM, bo
   if (sensordata) {
     if (m.acc_sens && !(m.disableflags & MRS_DSBL_SENSOR)) { [[clang::noinline]] rne_post<G>(ENV_ARGS, ncon); }
     if (!(m.diag_skip & 1)) MRS_CALL(G, sensors<G>(ENV_ARGS, sensordata, !helper));
+    if (m.nsens_more && !(m.disableflags & MRS_DSBL_SENSOR)) { [[clang::noinline]] sensors_more<G>(ENV_ARGS, sensordata, ncon); }
   }
   PH_END(ph_acc, PH_SENS);
   return ncon;
@@ -7689,7 +7803,7 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
     #pragma unroll 1
     for (int i = threadIdx.x; i < 17 * m.nrfblk; i += blockDim.x) shr[m.shr_blk + i] = m.rfblk[i];
     #pragma unroll 1
-    for (int i = threadIdx.x; i < 16 * m.nsens_other; i += blockDim.x) shr[m.shr_sens + i] = m.sensrec[i];
+    for (int i = threadIdx.x; i < m.shr_fric - m.shr_sens; i += blockDim.x) shr[m.shr_sens + i] = m.sensrec[i];
     #pragma unroll 1
     for (int i = threadIdx.x; i < 4 * m.nfric; i += blockDim.x) shr[m.shr_fric + i] = m.fricrec[i];
     #pragma unroll 1

@@ -8,10 +8,11 @@
 // for limit and friction), <freejoint>, geoms (plane/sphere/capsule/ellipsoid/cylinder/box/mesh,
 // fromto, contype/conaffinity/condim/group/priority, friction, margin, gap, solmix, solref, solimp,
 // rgba, material, mass/density), <asset> meshes (OBJ/STL files or inline vertex/face, scale; meshdir)
-// and materials (rgba), sites, cameras (fixed), <frame>, <replicate count sep offset euler> with sensor
-// replication and zero-padded suffixes, actuators (motor/position/velocity/general with
-// dampratio->kv), sensors (rangefinder, jointpos, jointvel, actuatorfrc, framepos, framequat, gyro,
-// accelerometer, force, torque), <statistic>, <visual><map znear zfar>, <keyframe><key>.
+// and materials (rgba), sites (type, size, fromto), cameras (fixed), <frame>, <replicate count sep offset
+// euler> with sensor replication and zero-padded suffixes, actuators (motor/position/velocity/general
+// with dampratio->kv), sensors (rangefinder, jointpos, jointvel, actuatorfrc, framepos, framequat, gyro,
+// accelerometer, force, torque, velocimeter, touch, framexaxis/yaxis/zaxis, framelinvel, frameangvel,
+// framelinacc, subtreecom, subtreelinvel), <statistic>, <visual><map znear zfar>, <keyframe><key>.
 //
 // The reference hands MJCF to MuJoCo's compiler at src/mujoco_system_interface.cpp:310,318
 // (mj_loadXML) and :398-399 (mj_parseXMLString + mj_compile).  MuJoCo's compiler is third-party
@@ -240,7 +241,12 @@ struct MeshRec {
   double pos[3] = {0, 0, 0}, quat[4] = {1, 0, 0, 0};
   double volume = 0, inertia[3] = {0, 0, 0}, half[3] = {0, 0, 0}, rbound = 0;
 };
-struct SiteRec { std::string name; double pos[3] = {0, 0, 0}, quat[4] = {1, 0, 0, 0}; };
+struct SiteRec {
+  std::string name;
+  double pos[3] = {0, 0, 0}, quat[4] = {1, 0, 0, 0};
+  int type = MRS_GEOM_SPHERE;  // MuJoCo's site defaults: a sphere of radius 0.005
+  double size[3] = {0.005, 0.005, 0.005};
+};
 struct CamRec {
   std::string name;
   double pos[3] = {0, 0, 0}, quat[4] = {1, 0, 0, 0}, fovy = 45;
@@ -1025,8 +1031,35 @@ struct Compiler {
     SiteRec s;
     s.name = elem_name(e, suffix);
     const DefaultClass* cls = resolve_class(e, childclass);
-    get_reals(e, cls, "site", "pos", s.pos, 3, true);
-    get_orientation(e, cls, "site", s.quat);
+    // shape (the touch sensor's zone): type, size and fromto as for geoms
+    std::string type;
+    if (get_str(e, cls, "site", "type", type)) {
+      if (type == "sphere") s.type = MRS_GEOM_SPHERE;
+      else if (type == "capsule") s.type = MRS_GEOM_CAPSULE;
+      else if (type == "ellipsoid") s.type = MRS_GEOM_ELLIPSOID;
+      else if (type == "cylinder") s.type = MRS_GEOM_CYLINDER;
+      else if (type == "box") s.type = MRS_GEOM_BOX;
+      else fail(e, "unsupported site type '" + type + "'");
+    }
+    get_reals(e, cls, "site", "size", s.size, 3);
+    double ft[6];
+    if (get_reals(e, cls, "site", "fromto", ft, 6, true)) {
+      if (s.type == MRS_GEOM_SPHERE) fail(e, "fromto requires capsule, cylinder, box or ellipsoid");
+      double d[3] = {ft[3] - ft[0], ft[4] - ft[1], ft[5] - ft[2]};
+      double len = norm3(d);
+      if (len < kMinVal) fail(e, "fromto points coincide");
+      for (int i = 0; i < 3; ++i) s.pos[i] = 0.5 * (ft[i] + ft[i + 3]);
+      quat_z2vec(s.quat, d);
+      if (s.type == MRS_GEOM_BOX || s.type == MRS_GEOM_ELLIPSOID) {
+        s.size[1] = s.size[0];
+        s.size[2] = len / 2;
+      } else {
+        s.size[1] = len / 2;
+      }
+    } else {
+      get_reals(e, cls, "site", "pos", s.pos, 3, true);
+      get_orientation(e, cls, "site", s.quat);
+    }
     frame.apply(s.pos, s.quat);
     return s;
   }
@@ -1164,15 +1197,22 @@ struct Compiler {
       int type, objtype, dim;
       std::string objname;
       if (tag == "rangefinder" || tag == "gyro" || tag == "accelerometer" || tag == "force" ||
-          tag == "torque") {
+          tag == "torque" || tag == "velocimeter" || tag == "touch") {
         objtype = MRS_OBJ_SITE;
         if (!get_str(e, cls, tag, "site", objname)) fail(e, "sensor requires 'site'");
         type = tag == "rangefinder" ? MRS_SENS_RANGEFINDER
                : tag == "gyro"      ? MRS_SENS_GYRO
                : tag == "accelerometer" ? MRS_SENS_ACCELEROMETER
                : tag == "force"     ? MRS_SENS_FORCE
-                                    : MRS_SENS_TORQUE;
-        dim = tag == "rangefinder" ? 1 : 3;
+               : tag == "torque"    ? MRS_SENS_TORQUE
+               : tag == "velocimeter" ? MRS_SENS_VELOCIMETER
+                                    : MRS_SENS_TOUCH;
+        dim = tag == "rangefinder" || tag == "touch" ? 1 : 3;
+      } else if (tag == "subtreecom" || tag == "subtreelinvel") {
+        objtype = MRS_OBJ_BODY;
+        if (!get_str(e, cls, tag, "body", objname)) fail(e, "sensor requires 'body'");
+        type = tag == "subtreecom" ? MRS_SENS_SUBTREECOM : MRS_SENS_SUBTREELINVEL;
+        dim = 3;
       } else if (tag == "jointpos" || tag == "jointvel") {
         objtype = MRS_OBJ_JOINT;
         if (!get_str(e, cls, tag, "joint", objname)) fail(e, "sensor requires 'joint'");
@@ -1183,16 +1223,28 @@ struct Compiler {
         if (!get_str(e, cls, tag, "actuator", objname)) fail(e, "sensor requires 'actuator'");
         type = MRS_SENS_ACTUATORFRC;
         dim = 1;
-      } else if (tag == "framepos" || tag == "framequat") {
+      } else if (tag == "framepos" || tag == "framequat" || tag == "framexaxis" || tag == "frameyaxis" ||
+                 tag == "framezaxis" || tag == "framelinvel" || tag == "frameangvel" || tag == "framelinacc") {
         std::string ot;
+        // relative frames are not supported: say so instead of sensing in the world frame
+        for (const char* ref : {"reftype", "refname"})
+          if (get_str(e, cls, tag, ref, ot))
+            fail(e, std::string("frame sensors relative to another frame ('") + ref + "') are not supported");
         if (!get_str(e, cls, tag, "objtype", ot) || !get_str(e, cls, tag, "objname", objname))
           fail(e, "frame sensor requires objtype and objname");
         if (ot == "site") objtype = MRS_OBJ_SITE;
         else if (ot == "body" || ot == "xbody") objtype = MRS_OBJ_BODY;
         else if (ot == "geom") objtype = MRS_OBJ_GEOM;
         else fail(e, "unsupported frame sensor objtype " + ot);
-        type = tag == "framepos" ? MRS_SENS_FRAMEPOS : MRS_SENS_FRAMEQUAT;
-        dim = tag == "framepos" ? 3 : 4;
+        type = tag == "framepos"      ? MRS_SENS_FRAMEPOS
+               : tag == "framequat"   ? MRS_SENS_FRAMEQUAT
+               : tag == "framexaxis"  ? MRS_SENS_FRAMEXAXIS
+               : tag == "frameyaxis"  ? MRS_SENS_FRAMEYAXIS
+               : tag == "framezaxis"  ? MRS_SENS_FRAMEZAXIS
+               : tag == "framelinvel" ? MRS_SENS_FRAMELINVEL
+               : tag == "frameangvel" ? MRS_SENS_FRAMEANGVEL
+                                      : MRS_SENS_FRAMELINACC;
+        dim = tag == "framequat" ? 4 : 3;
       } else {
         fail(e, "unsupported sensor type");
       }
@@ -1383,6 +1435,8 @@ struct Compiler {
         m.site_pos.insert(m.site_pos.end(), S.pos, S.pos + 3);
         quat_normalize(S.quat);
         m.site_quat.insert(m.site_quat.end(), S.quat, S.quat + 4);
+        m.site_type.push_back(S.type);
+        m.site_size.insert(m.site_size.end(), S.size, S.size + 3);
         ++m.nsite;
       }
       for (CamRec& C : B.cams) {
@@ -2294,6 +2348,7 @@ mrs_model_view Model::view() const {
   v.nmeshpolyvert = static_cast<int>(mesh_polyvert.size());
   MRS_V(mesh_polyadr); MRS_V(mesh_polynum); MRS_V(mesh_polyvertadr); MRS_V(mesh_polyvert); MRS_V(mesh_polynormal);
   v.mesh_polyvertnum = mesh_polynum_v.empty() ? nullptr : mesh_polynum_v.data();
+  MRS_V(site_type); MRS_V(site_size);
 #undef MRS_V
   return v;
 }

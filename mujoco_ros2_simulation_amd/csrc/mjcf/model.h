@@ -40,8 +40,8 @@ struct Model {
   std::vector<double> geom_size, geom_pos, geom_quat, geom_rbound, geom_friction, geom_margin,
       geom_gap, geom_solmix, geom_solref, geom_solimp, geom_rgba;
 
-  std::vector<int> site_bodyid;
-  std::vector<double> site_pos, site_quat;
+  std::vector<int> site_bodyid, site_type;
+  std::vector<double> site_pos, site_quat, site_size;
 
   std::vector<int> cam_bodyid, cam_resolution;
   std::vector<double> cam_pos, cam_quat, cam_fovy;

@@ -29,6 +29,8 @@ OBJ_BODY, OBJ_JOINT, OBJ_GEOM, OBJ_SITE, OBJ_CAMERA, OBJ_ACTUATOR, OBJ_SENSOR = 
 OBJ_TENDON = 18
 SENS_ACCELEROMETER, SENS_GYRO, SENS_FORCE, SENS_TORQUE, SENS_RANGEFINDER = 1, 3, 4, 5, 7
 SENS_JOINTPOS, SENS_JOINTVEL, SENS_ACTUATORFRC, SENS_FRAMEPOS, SENS_FRAMEQUAT = 9, 10, 15, 25, 26
+SENS_TOUCH, SENS_VELOCIMETER, SENS_FRAMEXAXIS, SENS_FRAMEYAXIS, SENS_FRAMEZAXIS = 0, 2, 27, 28, 29
+SENS_FRAMELINVEL, SENS_FRAMEANGVEL, SENS_FRAMELINACC, SENS_SUBTREECOM, SENS_SUBTREELINVEL = 30, 31, 32, 34, 35
 BIAS_NONE, BIAS_AFFINE = 0, 1
 RESTATE_NEWTON_REFINE, RESTATE_PGS_ELLIPTIC_BLOCK, RESTATE_NO_MPR_POLISH, RESTATE_NO_MULTICCD = 1, 2, 4, 8
 (FIELD_QPOS, FIELD_QVEL, FIELD_CTRL, FIELD_QFRC_APPLIED, FIELD_QACC_WARMSTART, FIELD_QACC,
@@ -146,6 +148,8 @@ _POLY_ARRAYS = [
     ("mesh_polyvertnum", "i", "nmeshpoly", 1), ("mesh_polyvert", "i", "nmeshpolyvert", 1),
     ("mesh_polynormal", "d", "nmeshpoly", 3),
 ]
+# site shapes (after the polygon block)
+_SITE_ARRAYS = [("site_type", "i", "nsite", 1), ("site_size", "d", "nsite", 3)]
 
 
 class ModelView(C.Structure):
@@ -168,7 +172,8 @@ class ModelView(C.Structure):
                 [(n, C.c_int) for n in _TEN_SIZES] +
                 [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _TEN_ARRAYS] +
                 [(n, C.c_int) for n in _POLY_SIZES] +
-                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _POLY_ARRAYS])
+                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _POLY_ARRAYS] +
+                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _SITE_ARRAYS])
 
 
 _lib = None
@@ -267,7 +272,7 @@ class Model:
         self.gravity = np.array(v.gravity[:])
         self.vis_headlight = np.array(v.vis_headlight[:])
         for name, kind, count, width in (_ARRAYS + _MESH_ARRAYS + _CONTACT_ARRAYS + _EQ_ARRAYS + _REND_ARRAYS +
-                                         _TEN_ARRAYS + _POLY_ARRAYS):
+                                         _TEN_ARRAYS + _POLY_ARRAYS + _SITE_ARRAYS):
             n = getattr(v, count)
             w = getattr(v, width) if isinstance(width, str) else width
             ptr = getattr(v, name)
