@@ -47,7 +47,13 @@ enum {
                                   built its rows inline; 0 in every correct run) */
   MRS_FIELD_NCON = 10,         /* 1,   int32: contacts found in the last step (output) */
   MRS_FIELD_SOLVER_NITER = 11, /* 1,   int32: constraint solver iterations of the last step (mjData.solver_niter) */
-  MRS_FIELD_COUNT = 12
+  MRS_FIELD_XFRC_APPLIED = 12, /* 6 * nbody, fp32: mjData.xfrc_applied, per body a world-frame force [0:3] then
+                                  torque [3:6] acting at the body's centre of mass (xipos); row 0 (the
+                                  world) is ignored.  Added to qfrc_smooth beside qfrc_applied and counted
+                                  as external by the force / torque sensors (mj_rnePostConstraint).  Its
+                                  buffer is made, zero-filled, on the first set / get_field_device /
+                                  device_ptr of the field; reading it before returns zeros */
+  MRS_FIELD_COUNT = 13
 };
 
 /* last error message of the calling thread ("" if none) */
@@ -114,6 +120,11 @@ int mrs_batch_set_ctrl_device(mrs_batch* b, const float* d_ctrl);
  * mrs_batch_set_field / mrs_batch_set_ctrl_device (which return to the batch's own buffer).  Reads
  * of the ctrl field return the bound buffer's values.  The buffer must stay valid while bound. */
 int mrs_batch_bind_ctrl_device(mrs_batch* b, const float* d_ctrl);
+/* xfrc_applied has no bind call: its own buffer is the one the kernel reads.  A write to
+ * mrs_batch_device_ptr(b, MRS_FIELD_XFRC_APPLIED) [n_envs][nbody][6] fp32 that is ordered on the batch
+ * stream takes effect at the next step / forward launch; like ctrl / qfrc_applied the wrenches are held
+ * over the n steps of a launch (and RK4's stages), mrs_batch_reset zeroes the reset envs' rows, and the
+ * NaN auto-reset keeps them. */
 
 /* replaces mj_step (src/mujoco_system_interface.cpp:1691,1731): advance every env n_steps times,
  * fused in one launch; ctrl / qfrc_applied are held constant (zero-order hold) across the n steps,

@@ -66,6 +66,11 @@ int mrsp_get_model(mrsp_system* s, int* sizes, double* timestep);
 int mrsp_get_data(mrsp_system* s, double* qpos, double* qvel, double* ctrl, double* sensordata, double* time);
 /* set_data(mjData*) (:1810-1814) with a get_data copy whose qpos / qvel / time are replaced */
 int mrsp_set_data(mrsp_system* s, const double* qpos, const double* qvel, double time);
+/* mjData.xfrc_applied of a get_data copy: its length 6 * nbody is returned, up to `max` values are
+ * copied (xfrc may be NULL); and set_data with a get_data copy whose xfrc_applied is replaced by
+ * xfrc[6 * nbody] (per body a world-frame force, then torque, at its centre of mass) */
+int mrsp_get_xfrc_applied(mrsp_system* s, double* xfrc, int max);
+int mrsp_set_xfrc_applied(mrsp_system* s, const double* xfrc);
 /* last /clock message (seconds) and the number published */
 double mrsp_clock(const mrsp_system* s, long* count);
 

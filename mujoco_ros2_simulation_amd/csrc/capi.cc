@@ -211,7 +211,10 @@ int mrs_batch_get_field(mrs_batch* b, int field, double* host, int env0, int n) 
 
 void* mrs_batch_device_ptr(mrs_batch* b, int field) {
   if (!b || field < 0 || field >= MRS_FIELD_COUNT) return nullptr;
-  return mrs::batch_device_ptr(b->impl, field);
+  // (xfrc_applied's buffer is made on first use, which can fail: NULL then, the code in mrs_last_status)
+  void* p = nullptr;
+  guarded([&] { p = mrs::batch_device_ptr(b->impl, field); });
+  return p;
 }
 
 int mrs_batch_set_ctrl_device(mrs_batch* b, const float* d_ctrl) {

@@ -2179,6 +2179,7 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
   S.stage = take(d.npair > 0 ? 64 * kMaxPairCon * 7 : 0);  // <= 64 lanes x 8 contacts x 7 floats
   S.efc_n = take(1);
   S.sens = take(std::max(1, m.nsensordata));
+  S.xfrc = take(1);
   S.total = off;
   b.d_dm = static_cast<DevModel*>(dalloc(b, sizeof(DevModel)));
   HIP_CHECK(hipMemcpyAsync(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice, b.stream));
@@ -2196,8 +2197,23 @@ int field_dim(const Model& m, int field) {
     case MRS_FIELD_WARNING: return 4;
     case MRS_FIELD_NCON: return 1;
     case MRS_FIELD_SOLVER_NITER: return 1;
+    case MRS_FIELD_XFRC_APPLIED: return 6 * m.nbody;
   }
   return -1;
+}
+// the per-body wrench buffer [n][nbody][6], made and zero-filled when the field is first used; from
+// then on the step kernel reads it (DevState::xfrc_applied, and DevModel::xfrc for the phases).  The
+// earlier launches have finished before the model block changes
+float* ensure_xfrc(BatchImpl& b) {
+  if (!b.st.xfrc_applied) {
+    HIP_CHECK(hipSetDevice(b.device));
+    float* p = static_cast<float*>(dalloc(b, static_cast<size_t>(b.n) * 6 * b.model->nbody * sizeof(float)));
+    HIP_CHECK(hipStreamSynchronize(b.stream));
+    b.dm.xfrc = p;
+    HIP_CHECK(hipMemcpy(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice));
+    b.st.xfrc_applied = p;
+  }
+  return b.st.xfrc_applied;
 }
 void* field_ptr(BatchImpl& b, int field) {
   switch (field) {
@@ -2213,6 +2229,7 @@ void* field_ptr(BatchImpl& b, int field) {
     case MRS_FIELD_WARNING: return b.st.warning;
     case MRS_FIELD_NCON: return b.st.ncon;
     case MRS_FIELD_SOLVER_NITER: return b.st.niter;
+    case MRS_FIELD_XFRC_APPLIED: return ensure_xfrc(b);
   }
   return nullptr;
 }
@@ -2354,6 +2371,11 @@ void batch_reset(BatchImpl* b, int key, int env0, int n) {
   batch_set(b, MRS_FIELD_TIME, t.data(), env0, n);
   std::vector<double> w(static_cast<size_t>(n) * 4, 0.0);
   batch_set(b, MRS_FIELD_WARNING, w.data(), env0, n);
+  if (b->st.xfrc_applied) {  // (mj_resetData zeroes xfrc_applied)
+    const size_t row = static_cast<size_t>(6) * m.nbody;
+    HIP_CHECK(hipMemsetAsync(b->st.xfrc_applied + env0 * row, 0, n * row * sizeof(float), b->stream));
+    HIP_CHECK(hipStreamSynchronize(b->stream));
+  }
 }
 
 void batch_set(BatchImpl* b, int field, const double* host, int env0, int n) {
@@ -2394,6 +2416,10 @@ void batch_get(BatchImpl* b, int field, double* host, int env0, int n) {
   if (n == 0 || dim == 0) return;
   HIP_CHECK(hipSetDevice(b->device));
   const size_t cnt = static_cast<size_t>(n) * dim;
+  if (field == MRS_FIELD_XFRC_APPLIED && !b->st.xfrc_applied) {  // never used: zeros, and no buffer made
+    std::fill(host, host + cnt, 0.0);
+    return;
+  }
   const char* src = field == MRS_FIELD_CTRL && b->ctrl_bound ? reinterpret_cast<const char*>(b->ctrl_bound)
                                                                : static_cast<const char*>(field_ptr(*b, field));
   if (field == MRS_FIELD_TIME) {

@@ -66,7 +66,8 @@ struct ScratchLayout {
       efc_quad,              // blocked mode: per pipe, its first 16 items (record | rows << 16)
       efc_fd,                // elliptic models: the PGS row forces in fp64 (2 floats per row)
       sens,                  // sensordata sink of idle lane groups (envs past n_envs)
-      efc_n;                 // rows of the dense layout of the last forward (int bits; -1: none stored)
+      efc_n,                 // rows of the dense layout of the last forward (int bits; -1: none stored)
+      xfrc;                  // the lane group's row of DevState::xfrc_applied (int bits; -1: an idle group, none)
   int total;
 };
 constexpr int kMaxPairCon = 8;  // contacts one geom pair can produce (box-box: the clipped face polygon)
@@ -219,6 +220,11 @@ struct DevModel {
   // (consecutive); rf_sw_plo / _phi: floor / ceil of the period
   int rf_sweep, rf_sw_n, rf_sw_full, rf_sw_adr0, rf_sw_plo, rf_sw_phi;
   float rf_sw[16];
+  // DevState::xfrc_applied again (null until the field is first used; batch.hip ensure_xfrc): the
+  // phases receive the model pointer only, so the wave-uniform test that guards every read of the
+  // wrenches is on this copy, a scalar load beside the phase's other model fields.  Plain global
+  // memory [n_envs][nbody][6], read once per forward pass
+  const float* xfrc;
 };
 constexpr int kRayBlock = 128;
 
@@ -249,6 +255,9 @@ struct DevState {
   int* ncon;     // [n_envs]
   int* niter;    // [n_envs] constraint solver iterations of the last step (mjData.solver_niter)
   float* scratch;
+  // [n_envs][nbody][6] per-body Cartesian wrenches (mjData.xfrc_applied: world-frame force, then
+  // torque, at the body's centre of mass); null until the field is first used (batch.hip ensure_xfrc)
+  float* xfrc_applied;
   float* geom_xpos;  // [n_envs][ngeom][3]  kinematics of the last forward (for the depth camera)
   float* geom_xmat;  // [n_envs][ngeom][9]
   float* cam_xpos;   // [n_envs][ncam][3]

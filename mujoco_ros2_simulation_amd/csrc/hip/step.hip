@@ -2617,6 +2617,42 @@ __device__ __forceinline__ void jac_col_blk(const lfloat* s, const LdsLayout& L,
   for (int i = 0; i < 3; ++i) col[i] = cd[3 + i] + cr[i];
 }
 
+// the lane group's row of the per-body wrenches (DevState::xfrc_applied [n_envs][nbody][6]; the row
+// index is in the group's scratch, step_kernel), null for an idle group.  Only called when the field
+// is in use (m.xfrc non-null, a wave-uniform test)
+__device__ __forceinline__ const gfloat* xfrc_row(const DevModel& m, const gfloat* scr) {
+  const int row = __float_as_int(scr[m.S.xfrc]);
+  return row < 0 ? nullptr : (const gfloat*)m.xfrc + (size_t)row * 6 * m.nbody;
+}
+
+// mj_xfrcAccumulate (batches that use xfrc_applied only): the joint-space force of the per-body
+// Cartesian wrenches on lane's dof j, sum over the bodies b of j's subtree (the others' Jacobian
+// columns are zero) of J_b(xipos_b)' f_b + axis_j' tau_b -- the translational column from jac_col, the
+// rotational one the angular half of cdof (zero for slide and free-translational dofs).  The wrenches
+// are read from global memory, 6 floats per body; bodies without a wrench cost that read alone
+template <int G>
+__device__ float xfrc_qfrc(ENV_PARAMS) {
+  ENV_UNPACK;
+  const gfloat* xf = xfrc_row(m, scr);
+  float q = 0;
+  if (xf && lane < m.nv) {
+    const int j = lane;
+    const auto dr = dof_tab<G>(m, j);
+    const int bj = __float_as_int(dr[10]), e = __float_as_int(dr[11]);
+    const float ang[3] = {s[L.cdof + 6 * j], s[L.cdof + 6 * j + 1], s[L.cdof + 6 * j + 2]};
+    #pragma unroll 1
+    for (int b = bj; b < e; ++b) {
+      float w[6];
+      for (int i = 0; i < 6; ++i) w[i] = xf[6 * b + i];
+      if (w[0] == 0 && w[1] == 0 && w[2] == 0 && w[3] == 0 && w[4] == 0 && w[5] == 0) continue;
+      float col[3], pnt[3] = {s[L.xipos + 3 * b], s[L.xipos + 3 * b + 1], s[L.xipos + 3 * b + 2]};
+      jac_col(m, s, b, pnt, j, col);
+      q += dot3(col, w) + dot3(ang, w + 3);
+    }
+  }
+  return q;
+}
+
 // mj_passive + mj_fwdActuation + qfrc_smooth + qacc_smooth (lane per dof)
 template <int G>
 __device__ MRS_PHASE float smooth_forces(ENV_PARAMS) {
@@ -2658,6 +2694,10 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS) {
     s[L.act_force + a] = force;
   }
   wsync();
+  // xfrc_applied beside qfrc_applied (no disable flag covers it); out of line, so a batch that never
+  // sets a wrench pays this scalar branch alone
+  float qx = 0;
+  if (m.xfrc) { [[clang::noinline]] qx = xfrc_qfrc<G>(ENV_ARGS); }
   float qfs = 0;
   if (lane < nv) {
     const int j = lane;
@@ -2710,6 +2750,7 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS) {
     }
     s[L.qfrc_passive + j] = pas;
     qfs = pas - s[L.qfrc_bias + j] + s[L.qfrc_applied + j] + qa;
+    if (m.xfrc) qfs += qx;
     s[L.qfrc_smooth + j] = qfs;
   }
   float qacc_s;
@@ -6375,6 +6416,9 @@ __device__ MRS_PHASE void rne_post(ENV_PARAMS, int ncon) {
     }
   }
   const gfloat* ff = scr + S.efc_f;
+  // xfrc_applied is part of cfrc_ext (batches that use the field only; null otherwise)
+  const gfloat* xf = nullptr;
+  if (m.xfrc) xf = xfrc_row(m, scr);
   #pragma unroll 1
   for (int b = lane; b < m.nbody; b += G) {
     float fi[6] = {0, 0, 0, 0, 0, 0};
@@ -6414,6 +6458,15 @@ __device__ MRS_PHASE void rne_post(ENV_PARAMS, int ncon) {
         cross3(tq, d, F);  // torque about the subtree com: (pos - com) x F
         const float sg = b == b2 ? -1.0f : 1.0f;  // cfrc_int subtracts cfrc_ext (+ for body2)
         for (int i = 0; i < 3; ++i) { fi[i] += sg * tq[i]; fi[3 + i] += sg * F[i]; }
+      }
+      if (xf) {
+        // the body's wrench acts at xipos: moved to the subtree com, then subtracted like the contacts'
+        float w[6];
+        for (int i = 0; i < 6; ++i) w[i] = xf[6 * b + i];
+        const float d[3] = {s[L.xipos + 3 * b] - c3[0], s[L.xipos + 3 * b + 1] - c3[1], s[L.xipos + 3 * b + 2] - c3[2]};
+        float tq[3];
+        cross3(tq, d, w);
+        for (int i = 0; i < 3; ++i) { fi[i] -= w[3 + i] + tq[i]; fi[3 + i] -= w[i]; }
       }
     }
     for (int i = 0; i < 6; ++i) s[L.cfrc + 6 * b + i] = fi[i];
@@ -7773,6 +7826,9 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
   }
   #pragma unroll 1
   for (int i = lane; i < (is_helper ? 0 : m.nu); i += G) s[L.ctrl + i] = st.ctrl[e * m.nu + i];
+  // xfrc_applied in use: the group's row of it for the phases (xfrc_row) -- a mirror group reads its
+  // primary's env, a group past n_envs none
+  if (st.xfrc_applied && lane == 0 && !is_helper) scr[m.S.xfrc] = __int_as_float(env < n_envs ? env : -1);
   if constexpr (G == 64) {
     #pragma unroll 1
     for (int t = lane; t < m.ntree; t += G) {

@@ -74,6 +74,10 @@ class MujocoSystemInterface : public hardware_interface::SystemInterface {
   // control -> sim, n steps, sim -> control (caller holds sim_mutex_); false if diverged
   bool advance_locked(int n);
   void pull_state_locked();
+  // mj_data_->xfrc_applied to env 0, once some entry is non-zero (from then on always: the batch
+  // makes the field's buffer on its first use, and a wrench must also be clearable)
+  void push_xfrc_locked();
+  bool xfrc_pushed_ = false;
 
   std::string model_path_;
   mjModel* mj_model_ = nullptr;         // owns the compiled model

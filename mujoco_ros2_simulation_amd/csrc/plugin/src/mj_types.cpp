@@ -58,7 +58,8 @@ mjData* mj_makeData(const mjModel* m) {
   d->nv = m->nv;
   d->nu = m->nu;
   d->nsensordata = m->nsensordata;
-  const size_t n = size_t(d->nq) + 5 * size_t(d->nv) + size_t(d->nu) + size_t(d->nsensordata);
+  d->nbody = m->nbody;
+  const size_t n = size_t(d->nq) + 5 * size_t(d->nv) + size_t(d->nu) + size_t(d->nsensordata) + 6 * size_t(d->nbody);
   d->buffer = new double[n > 0 ? n : 1]();
   double* p = d->buffer;
   auto take = [&p](int k) { double* r = p; p += k; return r; };
@@ -70,17 +71,20 @@ mjData* mj_makeData(const mjModel* m) {
   d->qfrc_applied = take(d->nv);
   d->qfrc_actuator = take(d->nv);
   d->sensordata = take(d->nsensordata);
+  d->xfrc_applied = take(6 * d->nbody);
   return d;
 }
 
 mjData* mj_copyData(mjData* dest, const mjModel* m, const mjData* src) {
   if (!m || !src) return nullptr;
-  if (src->nq != m->nq || src->nv != m->nv || src->nu != m->nu || src->nsensordata != m->nsensordata)
+  if (src->nq != m->nq || src->nv != m->nv || src->nu != m->nu || src->nsensordata != m->nsensordata ||
+      src->nbody != m->nbody)
     return nullptr;
   if (!dest) dest = mj_makeData(m);
-  else if (dest->nq != m->nq || dest->nv != m->nv || dest->nu != m->nu || dest->nsensordata != m->nsensordata)
+  else if (dest->nq != m->nq || dest->nv != m->nv || dest->nu != m->nu || dest->nsensordata != m->nsensordata ||
+           dest->nbody != m->nbody)
     return nullptr;
-  const size_t n = size_t(m->nq) + 5 * size_t(m->nv) + size_t(m->nu) + size_t(m->nsensordata);
+  const size_t n = size_t(m->nq) + 5 * size_t(m->nv) + size_t(m->nu) + size_t(m->nsensordata) + 6 * size_t(m->nbody);
   if (dest != src) std::memcpy(dest->buffer, src->buffer, n * sizeof(double));
   dest->time = src->time;
   return dest;

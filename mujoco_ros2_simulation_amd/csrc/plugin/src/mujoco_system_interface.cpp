@@ -632,7 +632,16 @@ void MujocoSystemInterface::pull_state_locked() {
   std::copy(d.qacc_warmstart, d.qacc_warmstart + d.nv, c.qacc_warmstart);
   std::copy(d.qfrc_actuator, d.qfrc_actuator + d.nv, c.qfrc_actuator);
   std::copy(d.sensordata, d.sensordata + d.nsensordata, c.sensordata);
+  std::copy(d.xfrc_applied, d.xfrc_applied + 6 * d.nbody, c.xfrc_applied);
   c.time = d.time;
+}
+
+void MujocoSystemInterface::push_xfrc_locked() {
+  const double* x = mj_data_->xfrc_applied;
+  const int n = 6 * mj_data_->nbody;
+  if (!xfrc_pushed_ && std::all_of(x, x + n, [](double v) { return v == 0; })) return;
+  xfrc_pushed_ = true;
+  mrs_batch_set_field(batch_, MRS_FIELD_XFRC_APPLIED, x, 0, 1);
 }
 
 bool MujocoSystemInterface::advance_locked(int n) {
@@ -641,6 +650,8 @@ bool MujocoSystemInterface::advance_locked(int n) {
   std::copy(mj_data_control_->qfrc_applied, mj_data_control_->qfrc_applied + view_.nv, mj_data_->qfrc_applied);
   if (view_.nu > 0) mrs_batch_set_field(batch_, MRS_FIELD_CTRL, mj_data_->ctrl, 0, 1);
   if (view_.nv > 0) mrs_batch_set_field(batch_, MRS_FIELD_QFRC_APPLIED, mj_data_->qfrc_applied, 0, 1);
+  // (xfrc_applied is the sim side's own, as in the reference, whose control -> sim copy leaves it alone)
+  push_xfrc_locked();
   double before[4], after[4];
   mrs_batch_get_field(batch_, MRS_FIELD_WARNING, before, 0, 1);
   if (mrs_batch_step(batch_, n) != MRS_OK || mrs_batch_sync(batch_) != MRS_OK) {
@@ -748,6 +759,7 @@ void MujocoSystemInterface::set_data(mjData* mj_data) {
     mrs_batch_set_field(batch_, MRS_FIELD_QACC_WARMSTART, mj_data_->qacc_warmstart, 0, 1);
     mrs_batch_set_field(batch_, MRS_FIELD_QFRC_APPLIED, mj_data_->qfrc_applied, 0, 1);
   }
+  push_xfrc_locked();
   if (view_.nu > 0) mrs_batch_set_field(batch_, MRS_FIELD_CTRL, mj_data_->ctrl, 0, 1);
   mrs_batch_set_field(batch_, MRS_FIELD_TIME, &mj_data_->time, 0, 1);
   mrs_batch_forward(batch_);

@@ -342,6 +342,28 @@ int mrsp_set_data(mrsp_system* s, const double* qpos, const double* qvel, double
   return 0;
 }
 
+int mrsp_get_xfrc_applied(mrsp_system* s, double* xfrc, int max) {
+  if (!s || !s->plugin) return fail("plugin not initialised");
+  mjData* d = nullptr;
+  s->plugin->get_data(d);
+  if (!d) return fail("get_data failed");
+  const int n = 6 * d->nbody;
+  if (xfrc) std::copy(d->xfrc_applied, d->xfrc_applied + std::min(n, std::max(max, 0)), xfrc);
+  mj_deleteData(d);
+  return n;
+}
+
+int mrsp_set_xfrc_applied(mrsp_system* s, const double* xfrc) {
+  if (!s || !s->plugin || !xfrc) return fail("plugin not initialised, or null argument");
+  mjData* d = nullptr;
+  s->plugin->get_data(d);
+  if (!d) return fail("get_data failed");
+  std::copy(xfrc, xfrc + 6 * d->nbody, d->xfrc_applied);
+  s->plugin->set_data(d);
+  mj_deleteData(d);
+  return 0;
+}
+
 double mrsp_clock(const mrsp_system* s, long* count) {
   if (!s || !s->plugin) return -1.0;
   auto pub = s->plugin->node()->find_publisher<rosgraph_msgs::msg::Clock>("/clock");

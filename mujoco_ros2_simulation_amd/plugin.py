@@ -54,6 +54,8 @@ def lib() -> C.CDLL:
             "mrsp_get_model": (I, [P, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
             "mrsp_get_data": (I, [P] + [C.POINTER(C.c_double)] * 5),
             "mrsp_set_data": (I, [P, C.POINTER(C.c_double), C.POINTER(C.c_double), D]),
+            "mrsp_get_xfrc_applied": (I, [P, C.POINTER(C.c_double), I]),
+            "mrsp_set_xfrc_applied": (I, [P, C.POINTER(C.c_double)]),
             "mrsp_lidar_update": (I, [P]),
             "mrsp_last_scan": (I, [P, S, F, I, F]),
             "mrsp_camera_update": (I, [P]),
@@ -218,6 +220,23 @@ class System:
         v = np.ascontiguousarray(qvel, dtype=np.float64)
         ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
         if lib().mrsp_set_data(self._h, ptr(q), ptr(v), float(time)) != 0:
+            raise PluginError(_err())
+
+    def get_xfrc_applied(self) -> np.ndarray:
+        """xfrc_applied [nbody][6] of a get_data copy of the shim mjData"""
+        n = lib().mrsp_get_xfrc_applied(self._h, None, 0)
+        if n < 0:
+            raise PluginError(_err())
+        out = np.zeros(n)
+        lib().mrsp_get_xfrc_applied(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), n)
+        return out.reshape(-1, 6)
+
+    def set_xfrc_applied(self, xfrc) -> None:
+        """set_data with a get_data copy whose xfrc_applied [nbody][6] is replaced"""
+        x = np.ascontiguousarray(xfrc, dtype=np.float64).reshape(-1)
+        if x.size != lib().mrsp_get_xfrc_applied(self._h, None, 0):
+            raise ValueError("xfrc_applied must have 6 values per body")
+        if lib().mrsp_set_xfrc_applied(self._h, x.ctypes.data_as(C.POINTER(C.c_double))) != 0:
             raise PluginError(_err())
 
     def clock(self) -> tuple[float, int]:

@@ -58,11 +58,13 @@ def flops_per_env_step(m: "sim.Model", nefc: int = None, pgs_iters: float = None
     return f
 
 
-def bytes_per_env_step(m: "sim.Model", steps_per_launch: int) -> float:
+def bytes_per_env_step(m: "sim.Model", steps_per_launch: int, xfrc: bool = False) -> float:
+    """xfrc: the batch uses xfrc_applied -- its wrenches (6 floats per body) are read from HBM every
+    step, not once per launch like the state held in LDS"""
     state_in = 4 * (m.nq + m.nv + m.nu + m.nv + m.nv) + 8      # qpos qvel ctrl qfrc_applied warmstart time
     state_out = 4 * (m.nq + m.nv + m.nv + m.nv + m.nv) + 8 + 4 + 48 * m.ngeom
     sens = 4 * m.nsensordata
-    return (state_in + state_out) / steps_per_launch + sens
+    return (state_in + state_out) / steps_per_launch + sens + (4 * 6 * m.nbody if xfrc else 0)
 
 
 def _ancestors(m, i):

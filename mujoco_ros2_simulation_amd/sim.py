@@ -34,7 +34,8 @@ SENS_FRAMELINVEL, SENS_FRAMEANGVEL, SENS_FRAMELINACC, SENS_SUBTREECOM, SENS_SUBT
 BIAS_NONE, BIAS_AFFINE = 0, 1
 RESTATE_NEWTON_REFINE, RESTATE_PGS_ELLIPTIC_BLOCK, RESTATE_NO_MPR_POLISH, RESTATE_NO_MULTICCD = 1, 2, 4, 8
 (FIELD_QPOS, FIELD_QVEL, FIELD_CTRL, FIELD_QFRC_APPLIED, FIELD_QACC_WARMSTART, FIELD_QACC,
- FIELD_QFRC_ACTUATOR, FIELD_SENSORDATA, FIELD_TIME, FIELD_WARNING, FIELD_NCON, FIELD_SOLVER_NITER) = range(12)
+ FIELD_QFRC_ACTUATOR, FIELD_SENSORDATA, FIELD_TIME, FIELD_WARNING, FIELD_NCON, FIELD_SOLVER_NITER,
+ FIELD_XFRC_APPLIED) = range(13)
 # ActuatorType (include/mujoco_ros2_control/data.hpp:43-51 numbering)
 ACT_UNKNOWN, ACT_MOTOR, ACT_POSITION, ACT_VELOCITY, ACT_CUSTOM = range(5)
 
@@ -332,7 +333,7 @@ class Model:
 _FIELD_DIM = {
     FIELD_QPOS: "nq", FIELD_QVEL: "nv", FIELD_CTRL: "nu", FIELD_QFRC_APPLIED: "nv", FIELD_QACC_WARMSTART: "nv",
     FIELD_QACC: "nv", FIELD_QFRC_ACTUATOR: "nv", FIELD_SENSORDATA: "nsensordata", FIELD_TIME: 1, FIELD_WARNING: 4,
-    FIELD_NCON: 1, FIELD_SOLVER_NITER: 1,
+    FIELD_NCON: 1, FIELD_SOLVER_NITER: 1, FIELD_XFRC_APPLIED: "6*nbody",
 }
 
 
@@ -349,12 +350,16 @@ class Batch:
 
     def _dim(self, field: int) -> int:
         d = _FIELD_DIM[field]
+        if field == FIELD_XFRC_APPLIED:
+            return 6 * self.model.nbody
         return getattr(self.model, d) if isinstance(d, str) else d
 
     def get(self, field: int, env0: int = 0, n: int | None = None) -> np.ndarray:
         n = self.n - env0 if n is None else n
         out = np.empty((n, self._dim(field)), dtype=np.float64)
         _check(lib().mrs_batch_get_field(self._h, field, out.ctypes.data, env0, n))
+        if field == FIELD_XFRC_APPLIED:  # per body: world-frame force, then torque
+            return out.reshape(n, self.model.nbody, 6)
         return out
 
     def set(self, field: int, values, env0: int = 0) -> None:
