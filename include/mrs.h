@@ -128,7 +128,11 @@ int mrs_batch_bind_ctrl_device(mrs_batch* b, const float* d_ctrl);
 
 /* replaces mj_step (src/mujoco_system_interface.cpp:1691,1731): advance every env n_steps times,
  * fused in one launch; ctrl / qfrc_applied are held constant (zero-order hold) across the n steps,
- * exactly as PhysicsLoop holds them between write() calls.  Asynchronous on the batch stream. */
+ * exactly as PhysicsLoop holds them between write() calls.  Asynchronous on the batch stream.
+ * sensordata afterwards is that of the last step's forward pass, as after n_steps mj_step calls; the
+ * steps before the last do not evaluate sensors (nothing can read their values, and sensors feed
+ * nothing back into the dynamics).  MRS_SENSORS_EVERY_STEP=1 in the environment at batch creation
+ * evaluates them every step instead: the same outputs, for A/B runs. */
 int mrs_batch_step(mrs_batch* b, int n_steps);
 /* replaces mj_forward (src/mujoco_system_interface.cpp:741,1771): recompute outputs (sensordata,
  * qfrc_actuator, qacc) for the current state without integrating */
@@ -194,8 +198,10 @@ int mrs_debug_phase_cycles(double* out, int n, int reset);
  * [7] kinematic trees with dofs, [8] workgroup-shared LDS floats, [9] lidar rays read from the
  * workgroup's LDS table (1) or the model block (0), [10] one workgroup per CU (16-lane groups kept for
  * tables past the two-per-CU budget), [11] waves per workgroup of a 16-lane batch (0 otherwise),
- * [12] helper waves (collision, rows, rays and the integrator factor beside the dynamics).  Returns
- * the number of values written. */
+ * [12] helper waves (collision, rows, rays and the integrator factor beside the dynamics), [13] the
+ * integrator's factor fused into the Cholesky phase, [14] ray sweep of a static planar lidar, [15]
+ * sensors evaluated on every step of a fused launch (MRS_SENSORS_EVERY_STEP=1) instead of the last
+ * only.  Returns the number of values written. */
 int mrs_debug_batch_layout(const mrs_batch* b, int* out, int n);
 
 #ifdef __cplusplus

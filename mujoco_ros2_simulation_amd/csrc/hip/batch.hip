@@ -1093,6 +1093,9 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
   d.impratio = static_cast<float>(m.impratio); d.ls_tolerance = static_cast<float>(m.ls_tolerance);
   // diagnostic phase ablation for profiling only (bit 0 sensors, 1 collision, 2 constraints)
   d.diag_skip = std::getenv("MRS_DIAG_SKIP") ? std::atoi(std::getenv("MRS_DIAG_SKIP")) : 0;
+  // a fused launch evaluates the sensors on its last step only (step.hip step_kernel);
+  // MRS_SENSORS_EVERY_STEP=1 evaluates them every step (A/B: the same outputs, bit for bit)
+  d.sens_every = std::getenv("MRS_SENSORS_EVERY_STEP") && std::atoi(std::getenv("MRS_SENSORS_EVERY_STEP")) != 0 ? 1 : 0;
   d.timestep = static_cast<float>(m.timestep);
   d.timestep_d = m.timestep;
   d.tolerance = static_cast<float>(m.tolerance);
@@ -2333,11 +2336,11 @@ void batch_free(BatchImpl* b) {
 int batch_num_envs(const BatchImpl* b) { return b->n; }
 
 int batch_layout(const BatchImpl* b, int* out, int n) {
-  const int v[15] = {b->group, b->dm.L.total, b->dm.S.total, b->dm.blocked, b->dm.pipe_w, b->dm.max_efc,
+  const int v[16] = {b->group, b->dm.L.total, b->dm.S.total, b->dm.blocked, b->dm.pipe_w, b->dm.max_efc,
                      b->dm.max_con, b->dm.ntree, b->dm.shr_total, b->dm.rf_common, b->g16_one_wg,
-                     b->group == 16 ? b->wpb16 : 0, b->helpers, b->dm.fuse_ih, b->dm.rf_sweep};
+                     b->group == 16 ? b->wpb16 : 0, b->helpers, b->dm.fuse_ih, b->dm.rf_sweep, b->dm.sens_every};
   int k = 0;
-  for (; k < n && k < 15; ++k) out[k] = v[k];
+  for (; k < n && k < 16; ++k) out[k] = v[k];
   return k;
 }
 

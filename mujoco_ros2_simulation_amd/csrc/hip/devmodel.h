@@ -127,6 +127,8 @@ struct DevModel {
   int acc_sens;   // bit 0: accelerometer / framelinacc (cacc), bit 1: force / torque / touch sensors (the row
                   // forces) present (mj_rnePostConstraint)
   int diag_skip;  // profiling ablation only (MRS_DIAG_SKIP); 0 in every measured/parity run
+  int sens_every;  // 1 (MRS_SENSORS_EVERY_STEP=1, A/B): every step of a fused launch evaluates and stores the
+                   // sensors; 0: only the last one, whose sensordata is what the launch leaves
   float timestep, tolerance, pgs_scale, gravity[3], impratio, ls_tolerance;
   double timestep_d;  // time is accumulated in fp64 like mjData.time
   // bodies

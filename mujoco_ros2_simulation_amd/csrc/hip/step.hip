@@ -6488,11 +6488,6 @@ __device__ MRS_PHASE void rne_post(ENV_PARAMS, int ncon) {
 // 1.98 at 1, 1.71 at 2), 2 at one env per wave (64-VGPR budget: 2.15 ms vs 2.38 at 1, 2.95 at 4)
 template <int G>
 struct RayBatch { static constexpr int value = G == 64 ? 2 : 4; };
-#ifdef MRS_DIAG_SENS_LAST
-#define MRS_SD_OK(p) ((p) != nullptr)
-#else
-#define MRS_SD_OK(p) true
-#endif
 
 // R rangefinders per lane in one pass over the geoms (mj_ray per sensor: nearest hit along the
 // site's +z over all visible geoms not on the site's body).  Each geom's pose is read from LDS once
@@ -6560,7 +6555,7 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
       // static split: start from the ray's hit on the world-welded geoms (never beaten: -1); later
       // chunks of ray geoms start from the earlier chunks' nearest hit in the output slot
       dist[j] = rf_mode == 2 ? (float)shared_lds(m)[m.shr_rfst + (act[j] ? k : 0)] : -1.0f;
-      if (kChunk && goff > 0) dist[j] = act[j] && MRS_SD_OK(sd) ? (float)sd[adr[j]] : -1.0f;
+      if (kChunk && goff > 0) dist[j] = act[j] ? (float)sd[adr[j]] : -1.0f;
     }
   } else {
 #pragma unroll
@@ -6583,7 +6578,7 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
         mat_vec(vec[j], bm, dl);
       }
       dist[j] = rf_mode == 2 ? (float)shared_lds(m)[m.shr_rfst + (act[j] ? k : 0)] : -1.0f;
-      if (kChunk && goff > 0) dist[j] = act[j] && MRS_SD_OK(sd) ? (float)sd[adr[j]] : -1.0f;
+      if (kChunk && goff > 0) dist[j] = act[j] ? (float)sd[adr[j]] : -1.0f;
     }
   }
   SUB_ADD(PH_SENS_SETUP, t_setup);
@@ -6726,12 +6721,11 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
       const int a = m.rf_common ? __float_as_int(shared_lds(m)[m.shr_rf + 4 * k + 3]) : __float_as_int(m.rfray[8 * k + 3]);
       return sd + a;
     };
-    const bool sd_ok = m.rf_mode == 1 || MRS_SD_OK(sd);
 #pragma unroll
     for (int j = 0; j < R; ++j) {
       if (m.rf_mode == 1) {
         if (act[j]) m.rf_static[ray_k(j)] = dist[j];
-      } else if (act[j] && sd_ok) {
+      } else if (act[j]) {
         sd[adr[j]] = dist[j];
       }
     }
@@ -6742,7 +6736,7 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
       const int rb = ray_of(k, p, v);
       const CPtr<float> rec = m.rgeom + 8 * (goff + i);
       const int g = __float_as_int(rec[0]), gb = __float_as_int(rec[2]), id = __float_as_int(rec[7]);
-      if (has && rb != gb && sd_ok) {
+      if (has && rb != gb) {
         gfloat* o = out_of(k);
         const float dcur = *o;
         const float dv[3] = {p[0] - se[L.gxpos + 3 * g], p[1] - se[L.gxpos + 3 * g + 1], p[2] - se[L.gxpos + 3 * g + 2]};
@@ -6792,7 +6786,7 @@ __device__ __forceinline__ void rangefinders(const DevModel& m, const lfloat* se
   for (int j = 0; j < R; ++j) {
     if (rf_mode == 1) {
       if (act[j]) m.rf_static[ray_k(j)] = dist[j];  // producer pass: the static hits
-    } else if (act[j] && MRS_SD_OK(sd)) {
+    } else if (act[j]) {
 #ifdef MRS_DIAG_SD_SINK
       asm volatile("" ::"v"(dist[j]));  // diagnostic build: the ray result is kept live, not stored
 #else
@@ -6947,7 +6941,7 @@ __device__ __forceinline__ void rays_sweep(ENV_PARAMS, gfloat* sensordata) {
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (k[j] < n && MRS_SD_OK(sensordata)) out[k[j]] = v[j];
+      if (k[j] < n) out[k[j]] = v[j];
   }
   // the other rows: the block passes' geom loop, MRS_SWEEP_ROWS rows per call
   #pragma unroll 1
@@ -7076,7 +7070,7 @@ __device__ __forceinline__ void rays_pass(ENV_PARAMS, gfloat* sensordata) {
           const int k = base + lane + j * G;
           if (k >= m.nrf) continue;
           if (m.rf_mode == 1) m.rf_static[k] = -1.0f;
-          else if (MRS_SD_OK(sensordata)) {
+          else {
             const int adr = m.rf_common ? __float_as_int(shared_lds(m)[m.shr_rf + 4 * k + 3]) : __float_as_int(m.rfray[8 * k + 3]);
             sensordata[adr] = m.rf_mode == 2 ? (float)shared_lds(m)[m.shr_rfst + k] : -1.0f;
           }
@@ -7129,7 +7123,6 @@ __device__ MRS_PHASE void sensors(ENV_PARAMS, gfloat* sensordata, bool rays = tr
   if constexpr (G == 64) sensordata = uniform_ptr(sensordata);
   if (m.disableflags & MRS_DSBL_SENSOR) return;
   if (rays) rays_pass<G>(ENV_ARGS, sensordata);
-  if (!MRS_SD_OK(sensordata)) return;
 #ifdef MRS_DIAG_NO_OTHER
   return;  // diagnostic build: rangefinders only
 #endif
@@ -7381,9 +7374,11 @@ template <int G>
 __device__ __forceinline__ void cholesky_ih(ENV_PARAMS);
 
 // full forward pass; returns the contact count.  With acc_bad, *acc_bad is the group's vote on qacc
-// (mj_checkAcc), taken from the solver's lane-per-dof result in registers
+// (mj_checkAcc), taken from the solver's lane-per-dof result in registers.  sens (wave-uniform): false
+// is mj_forwardSkip(skipsensor) -- the RK4 stages, and the steps of a fused launch whose sensordata
+// the launch's last step overwrites (step_kernel); sensordata is not read then
 template <int G, bool kPrimal = false, bool kHot = false>
-__device__ MRS_PHASE int forward(ENV_PARAMS, gfloat* sensordata PH_ACC_PARAM, bool helper = false,
+__device__ MRS_PHASE int forward(ENV_PARAMS, gfloat* sensordata, bool sens PH_ACC_PARAM, bool helper = false,
                                  bool* acc_bad = nullptr) {
   ENV_UNPACK;
   if constexpr (G == 64) sensordata = uniform_ptr(sensordata);
@@ -7434,8 +7429,10 @@ __device__ MRS_PHASE int forward(ENV_PARAMS, gfloat* sensordata PH_ACC_PARAM, bo
   if (lane < m.nv) s[L.qacc + lane] = qacc;
   if (acc_bad) *acc_bad = gany<G>(lane < m.nv && is_bad(qacc));
   wsync();
-  // sensordata == nullptr: mj_forwardSkip(skipsensor) (the RK4 stages)
-  if (sensordata) {
+  // one scalar branch around rne_post, sensors and sensors_more together (nothing after them in the
+  // step reads what they write: rne_post's L.cacc / L.cfrc / L.crb are rewritten by the next forward's
+  // rne before its first read, and no integrator reads them)
+  if (sens) {
     if (m.acc_sens && !(m.disableflags & MRS_DSBL_SENSOR)) { [[clang::noinline]] rne_post<G>(ENV_ARGS, ncon); }
     if (!(m.diag_skip & 1)) MRS_CALL(G, sensors<G>(ENV_ARGS, sensordata, !helper));
     if (m.nsens_more && !(m.disableflags & MRS_DSBL_SENSOR)) { [[clang::noinline]] sensors_more<G>(ENV_ARGS, sensordata, ncon); }
@@ -7911,7 +7908,8 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
       }
       if (lane == 0) s[L.hcon] = __int_as_float(nc + 65536 * (nr + 1));
       helper_barrier(true);
-      MRS_CALL(G, rays_pass<G>(ENV_ARGS, sensordata));
+      // the rays of the launch's last step only, like the physics wave's sensors (the step loop below)
+      if (m.sens_every || step == n_steps - 1) MRS_CALL(G, rays_pass<G>(ENV_ARGS, sensordata));
       // the integrator's factor of M + h D (the physics wave solves with it after B)
       if (L.Lh != 0) MRS_CALL(G, integrate_prefactor<G>(ENV_ARGS));
       helper_barrier(true);
@@ -7935,19 +7933,18 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
         if (!(m.disableflags & MRS_DSBL_AUTORESET)) { [[clang::noinline]] reset_env<G>(ENV_ARGS); time = 0; }
       }
     }
-#ifdef MRS_DIAG_SENS_LAST
-    // diagnostic build: sensors evaluated and stored on the last step of the launch only
-    gfloat* sd_step = (kForwardOnly || step == n_steps - 1) ? sensordata : nullptr;
-#else
-    gfloat* sd_step = sensordata;
-#endif
+    // sensors on the launch's last step only: the sensordata after n mj_steps is that of the last
+    // step's forward pass, each earlier step's is overwritten unread (sensors feed nothing back into
+    // the dynamics).  DevModel::sens_every evaluates them every step (A/B); mrs_batch_forward always
+    // does.  A scalar: one s_cbranch around the phase, no per-lane pointer select
+    const bool sens = kForwardOnly || m.sens_every || step == n_steps - 1;
     bool acc_bad = false;
-    MRS_CALL(G, ncon = (forward<G, kPrimal, helpers && !kPrimal>(ENV_ARGS, sd_step PH_ACC_ARG, helpers, &acc_bad)));
+    MRS_CALL(G, ncon = (forward<G, kPrimal, helpers && !kPrimal>(ENV_ARGS, sensordata, sens PH_ACC_ARG, helpers, &acc_bad)));
     if (helpers) helper_barrier(false);  // barrier B: this step's rays are stored
 #if MRS_EXT
     // rangefinders of a model with more than 32 ray geoms (sensors() leaves them to this call)
-    if (m.nrgeom > 32 && m.nrf > 0 && !(m.disableflags & MRS_DSBL_SENSOR))
-      [[clang::noinline]] rays_chunked<G>(ENV_ARGS, sd_step);
+    if (sens && m.nrgeom > 32 && m.nrf > 0 && !(m.disableflags & MRS_DSBL_SENSOR))
+      [[clang::noinline]] rays_chunked<G>(ENV_ARGS, sensordata);
 #endif
     if (kForwardOnly) break;
     bool redo = false;
@@ -7962,10 +7959,10 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
     // forward() is entered by the whole wave; for envs that were not reset it recomputes the
     // same outputs from the same state
     if (__any(redo)) {  // rare
-      [[clang::noinline]] ncon = forward<G, kPrimal>(ENV_ARGS, sd_step PH_ACC_ARG);
+      [[clang::noinline]] ncon = forward<G, kPrimal>(ENV_ARGS, sensordata, sens PH_ACC_ARG);
 #if MRS_EXT
-      if (m.nrgeom > 32 && m.nrf > 0 && !(m.disableflags & MRS_DSBL_SENSOR))
-        [[clang::noinline]] rays_chunked<G>(ENV_ARGS, sd_step);
+      if (sens && m.nrgeom > 32 && m.nrf > 0 && !(m.disableflags & MRS_DSBL_SENSOR))
+        [[clang::noinline]] rays_chunked<G>(ENV_ARGS, sensordata);
 #endif
     }
     if (m.integrator == MRS_INT_RK4) {
@@ -7973,7 +7970,7 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
       #pragma unroll 1
       for (int stage = 1; stage < 4; ++stage) {
         [[clang::noinline]] rk4_stage<G>(ENV_ARGS, stage);
-        [[clang::noinline]] ncon = forward<G, kPrimal>(ENV_ARGS, nullptr PH_ACC_ARG);
+        [[clang::noinline]] ncon = forward<G, kPrimal>(ENV_ARGS, nullptr, false PH_ACC_ARG);
       }
       [[clang::noinline]] rk4_final<G>(ENV_ARGS);
     } else {

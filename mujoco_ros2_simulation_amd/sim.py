@@ -337,6 +337,13 @@ _FIELD_DIM = {
 }
 
 
+# Batch.layout(): the values of mrs_debug_batch_layout, in order (sensors_every_step: 1 under
+# MRS_SENSORS_EVERY_STEP=1, else a fused launch evaluates sensors on its last step only)
+LAYOUT_KEYS = ["group", "lds_floats", "scratch_floats", "blocked", "pipe_w", "max_efc", "max_con", "ntree",
+               "shared_floats", "rf_common", "one_workgroup_per_cu", "waves_per_workgroup", "helper_waves",
+               "fused_integrator_factor", "ray_sweep", "sensors_every_step"]
+
+
 class Batch:
     """N independent environments of one model on one GPU (N x mjData analogue)."""
 
@@ -374,11 +381,9 @@ class Batch:
     def layout(self) -> dict:
         """kernel configuration of this batch (diagnostics): group width, LDS and scratch floats per
         env, blocked mode, pipe width, row and contact capacity, kinematic trees"""
-        out = np.zeros(15, dtype=np.int32)
-        k = lib().mrs_debug_batch_layout(self._h, out.ctypes.data, 15)
-        keys = ["group", "lds_floats", "scratch_floats", "blocked", "pipe_w", "max_efc", "max_con", "ntree",
-                "shared_floats", "rf_common", "one_workgroup_per_cu", "waves_per_workgroup", "helper_waves",
-                "fused_integrator_factor", "ray_sweep"]
+        out = np.zeros(len(LAYOUT_KEYS), dtype=np.int32)
+        k = lib().mrs_debug_batch_layout(self._h, out.ctypes.data, len(LAYOUT_KEYS))
+        keys = LAYOUT_KEYS
         return dict(zip(keys[:k], out[:k].tolist()))
 
     def step(self, n_steps: int = 1) -> None:
