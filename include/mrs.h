@@ -103,6 +103,44 @@ int mrs_batch_set_stream(mrs_batch* b, void* hip_stream);
 /* mj_resetData / mj_resetDataKeyframe for envs [env0, env0+n): key < 0 resets to qpos0 */
 int mrs_batch_reset(mrs_batch* b, int key, int env0, int n);
 
+/* ---- device-side masked reset (no reference counterpart: the reference resets one mjData on the
+ * host, mj_resetData / mj_resetDataKeyframe; here episodes end in scattered envs of a batch whose
+ * training loop stays on the GPU).
+ *
+ * A start index k addresses a start state: -1 is qpos0 (zero qvel and ctrl, time 0), 0 .. nkey-1 the
+ * model's keyframe k, nkey .. nkey+P-1 row k - nkey of the batch's pool of P runtime start states.
+ * The model's keyframes and qpos0 are uploaded to a device table at batch creation and the pool lives
+ * in HBM as fp32 in the state fields' layout, so the reset kernel reads everything from device memory.
+ *
+ * replace the batch's pool of start states: `count` rows, host fp64 qpos [count][nq] and
+ * qvel [count][nv] (qvel may be NULL: zeros).  count == 0 frees the pool.  Rows are copied as given,
+ * as mj_resetDataKeyframe copies a keyframe (quaternions are not renormalised); a pool row has
+ * ctrl = 0 and time = 0.  Returns when the host rows have been read. */
+int mrs_batch_set_start_states(mrs_batch* b, const double* qpos, const double* qvel, int count);
+/* same from device fp32 buffers, copied device-to-device, asynchronous on the batch stream (the
+ * buffers may be reused once that copy has run).  Only a pool that grows past the largest count it has
+ * held, or is freed, waits for the queued work that may still read the old rows */
+int mrs_batch_set_start_states_device(mrs_batch* b, const float* d_qpos, const float* d_qvel, int count);
+/* rows in the pool (P above) */
+int mrs_batch_num_start_states(const mrs_batch* b);
+/* reset the envs e with d_mask[e] != 0 (uint8 [n_envs], a torch.bool tensor's storage), each to
+ * the start index d_key[e] (int32 [n_envs]) or, with d_key == NULL, to `key`.  One launch,
+ * asynchronous on the batch stream, no host synchronisation: stream order alone places it after the
+ * steps and pool copies queued before and ahead of the steps queued after.  A masked env gets what
+ * mrs_batch_reset writes: qpos, qvel, ctrl and time of its start state, qfrc_applied,
+ * qacc_warmstart and the four warning counters zeroed, and its xfrc_applied rows zeroed if that
+ * buffer exists (it is not made here); the output fields keep their values.  An unmasked env is not
+ * written at all.  Unlike mrs_batch_reset this call keeps a ctrl buffer bound by
+ * mrs_batch_bind_ctrl_device: while one is bound neither that buffer (the caller's) nor the batch's
+ * own ctrl is written, and the launches go on reading the bound buffer -- the call to prefer in a bound
+ * loop.  The scalar `key` is checked here (>= nkey + P: MRS_ERR_INVALID); a per-env index cannot be
+ * checked without a synchronisation, so an index outside [-1, nkey + P) resets that env to qpos0 (as -1).
+ * The mask and the key array are only read. */
+int mrs_batch_reset_masked_device(mrs_batch* b, const unsigned char* d_mask, const int* d_key, int key);
+/* same with host arrays [n_envs] (staged to the device on the batch stream; returns when they have
+ * been read, without waiting for the reset itself); `keys` may be NULL */
+int mrs_batch_reset_masked(mrs_batch* b, const unsigned char* mask, const int* keys, int key);
+
 /* host <-> device state copies for envs [env0, env0+n), host layout [n][dim] fp64.
  * set_* replace the control->sim copies mju_copy(ctrl/qfrc_applied) at
  * src/mujoco_system_interface.cpp:1688-1689,1728-1729 and set_initial_pose/keyframe writes

@@ -195,6 +195,36 @@ int mrs_batch_reset(mrs_batch* b, int key, int env0, int n) {
   });
 }
 
+int mrs_batch_set_start_states(mrs_batch* b, const double* qpos, const double* qvel, int count) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_set_start_states(b->impl, qpos, qvel, count);
+  });
+}
+
+int mrs_batch_set_start_states_device(mrs_batch* b, const float* d_qpos, const float* d_qvel, int count) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_set_start_states_device(b->impl, d_qpos, d_qvel, count);
+  });
+}
+
+int mrs_batch_num_start_states(const mrs_batch* b) { return b ? mrs::batch_num_start_states(b->impl) : 0; }
+
+int mrs_batch_reset_masked_device(mrs_batch* b, const unsigned char* d_mask, const int* d_key, int key) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_reset_masked_device(b->impl, d_mask, d_key, key);
+  });
+}
+
+int mrs_batch_reset_masked(mrs_batch* b, const unsigned char* mask, const int* keys, int key) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_reset_masked(b->impl, mask, keys, key);
+  });
+}
+
 int mrs_batch_set_field(mrs_batch* b, int field, const double* host, int env0, int n) {
   return guarded([&] {
     if (!b || !host) throw std::invalid_argument("null argument");

@@ -18,6 +18,12 @@ int batch_num_envs(const BatchImpl* b);
 int batch_layout(const BatchImpl* b, int* out, int n);  // diagnostics: kernel configuration
 void batch_set_stream(BatchImpl* b, void* stream);
 void batch_reset(BatchImpl* b, int key, int env0, int n);
+// start-state pool (count rows; qvel may be null: zeros; count 0 frees it) and the masked reset
+void batch_set_start_states(BatchImpl* b, const double* qpos, const double* qvel, int count);
+void batch_set_start_states_device(BatchImpl* b, const float* d_qpos, const float* d_qvel, int count);
+int batch_num_start_states(const BatchImpl* b);
+void batch_reset_masked_device(BatchImpl* b, const unsigned char* d_mask, const int* d_key, int key);
+void batch_reset_masked(BatchImpl* b, const unsigned char* mask, const int* keys, int key);
 void batch_set(BatchImpl* b, int field, const double* host, int env0, int n);
 void batch_get(BatchImpl* b, int field, double* host, int env0, int n);
 void* batch_device_ptr(BatchImpl* b, int field);

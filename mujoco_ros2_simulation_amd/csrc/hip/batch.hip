@@ -872,6 +872,56 @@ __global__ __launch_bounds__(256) void depth_kernel_mesh(const int* geom_type, c
   }
 }
 
+// ------------------------------------------------------------------ masked reset kernel
+// One 16-lane group per env.  The group of an env whose mask byte is set copies the env's start
+// state (a row of the model's table -- row 0 qpos0, row 1 + k keyframe k -- or of the batch's pool)
+// into the state fields and clears what batch_reset clears; the group of an unmasked env returns
+// before its first store, so such an env's rows are never written.  The tables, the pool, the mask
+// and the key array are only read.
+struct ResetArgs {
+  const unsigned char* mask;  // [n]
+  const int* keys;            // [n] start indices, or null: `key` for every env
+  int key, n, nq, nv, nu, nx, nkey, npool;
+  const float *tab_qpos, *tab_qvel, *tab_ctrl;  // [1 + nkey][nq | nv | nu]
+  const double* tab_time;                       // [1 + nkey]
+  const float *pool_qpos, *pool_qvel;           // [npool][nq | nv]
+  float *qpos, *qvel, *ctrl, *qfrc_applied, *qacc_ws, *xfrc;  // ctrl / xfrc null: not written
+  double* time;
+  int* warning;
+};
+__global__ __launch_bounds__(256) void reset_masked_kernel(const ResetArgs a) {
+  const size_t e = (static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x) >> 4;
+  const int lane = threadIdx.x & 15;
+  if (e >= static_cast<size_t>(a.n) || !a.mask[e]) return;
+  int k = a.keys ? a.keys[e] : a.key;
+  if (k < -1 || k >= a.nkey + a.npool) k = -1;  // (an index outside the table and the pool: qpos0)
+  const float *sq, *sv, *sc = nullptr;  // (a pool row has no ctrl: zeros)
+  double t = 0;
+  if (k < a.nkey) {
+    const size_t row = static_cast<size_t>(k + 1);
+    sq = a.tab_qpos + row * a.nq;
+    sv = a.tab_qvel + row * a.nv;
+    sc = a.tab_ctrl + row * a.nu;
+    t = a.tab_time[row];
+  } else {
+    const size_t row = static_cast<size_t>(k - a.nkey);
+    sq = a.pool_qpos + row * a.nq;
+    sv = a.pool_qvel + row * a.nv;
+  }
+  for (int i = lane; i < a.nq; i += 16) a.qpos[e * a.nq + i] = sq[i];
+  for (int i = lane; i < a.nv; i += 16) {
+    a.qvel[e * a.nv + i] = sv[i];
+    a.qfrc_applied[e * a.nv + i] = 0;
+    a.qacc_ws[e * a.nv + i] = 0;
+  }
+  if (a.ctrl)
+    for (int i = lane; i < a.nu; i += 16) a.ctrl[e * a.nu + i] = sc ? sc[i] : 0.0f;
+  if (a.xfrc)
+    for (int i = lane; i < a.nx; i += 16) a.xfrc[e * a.nx + i] = 0;
+  if (lane < 4) a.warning[e * 4 + lane] = 0;
+  if (lane == 4) a.time[e] = t;
+}
+
 // ------------------------------------------------------------------ packing helpers
 struct Packer {
   std::vector<float> f;
@@ -913,6 +963,16 @@ struct BatchImpl {
   // a caller's device buffer [n][nu] the step launches read ctrl from (batch_bind_ctrl_device; null:
   // st.ctrl, the batch's own buffer)
   const float* ctrl_bound = nullptr;
+  // start states of the masked reset (reset_masked_kernel), fp32 in the state fields' layout: the
+  // model's table [1 + nkey] (row 0 qpos0 with zero qvel / ctrl / time, row 1 + k keyframe k; made at
+  // batch creation) and the runtime pool [pool_n] of batch_set_start_states (capacity pool_cap rows)
+  float *tab_qpos = nullptr, *tab_qvel = nullptr, *tab_ctrl = nullptr;
+  double* tab_time = nullptr;
+  float *pool_qpos = nullptr, *pool_qvel = nullptr;
+  int pool_n = 0, pool_cap = 0;
+  // device staging of batch_reset_masked's host mask and keys ([n] each, made on first use)
+  unsigned char* mask_stage = nullptr;
+  int* key_stage = nullptr;
   void* dblock_f = nullptr;
   void* dblock_i = nullptr;
   std::vector<void*> allocs;
@@ -2237,6 +2297,56 @@ void* field_ptr(BatchImpl& b, int field) {
   return nullptr;
 }
 
+// the model's start states as the masked reset reads them: qpos0 and the keyframes in one device
+// table, converted to fp32 exactly as batch_reset's rows are (key_time stays fp64, like the time field)
+void upload_start_table(BatchImpl& b) {
+  const Model& m = *b.model;
+  const size_t rows = static_cast<size_t>(m.nkey) + 1;
+  std::vector<float> q(rows * m.nq), v(rows * m.nv, 0.0f), c(rows * m.nu, 0.0f);
+  std::vector<double> t(rows, 0.0);
+  for (int i = 0; i < m.nq; ++i) q[i] = static_cast<float>(m.qpos0[i]);
+  for (int k = 0; k < m.nkey; ++k) {
+    const size_t r = static_cast<size_t>(k) + 1, s = static_cast<size_t>(k);
+    for (int i = 0; i < m.nq; ++i) q[r * m.nq + i] = static_cast<float>(m.key_qpos[s * m.nq + i]);
+    for (int i = 0; i < m.nv; ++i) v[r * m.nv + i] = static_cast<float>(m.key_qvel[s * m.nv + i]);
+    for (int i = 0; i < m.nu; ++i) c[r * m.nu + i] = static_cast<float>(m.key_ctrl[s * m.nu + i]);
+    t[r] = m.key_time[k];
+  }
+  b.tab_qpos = static_cast<float*>(dalloc(b, q.size() * sizeof(float)));
+  b.tab_qvel = static_cast<float*>(dalloc(b, v.size() * sizeof(float)));
+  b.tab_ctrl = static_cast<float*>(dalloc(b, c.size() * sizeof(float)));
+  b.tab_time = static_cast<double*>(dalloc(b, t.size() * sizeof(double)));
+  auto put = [&](void* dst, const void* src, size_t bytes) {
+    if (bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, b.stream));
+  };
+  put(b.tab_qpos, q.data(), q.size() * sizeof(float));
+  put(b.tab_qvel, v.data(), v.size() * sizeof(float));
+  put(b.tab_ctrl, c.data(), c.size() * sizeof(float));
+  put(b.tab_time, t.data(), t.size() * sizeof(double));
+  HIP_CHECK(hipStreamSynchronize(b.stream));
+}
+
+// room for `count` pool rows.  A pool that grows past its capacity, or is freed (count 0), waits for
+// the queued work that may still read the old rows before releasing them; otherwise nothing waits
+void reserve_pool(BatchImpl& b, int count) {
+  if (count < 0) throw std::invalid_argument("negative start-state count");
+  HIP_CHECK(hipSetDevice(b.device));
+  if (count != 0 && count <= b.pool_cap) return;
+  if (b.pool_qpos || b.pool_qvel) {
+    HIP_CHECK(hipStreamSynchronize(b.stream));
+    HIP_CHECK(hipFree(b.pool_qpos));
+    b.pool_qpos = nullptr;
+    HIP_CHECK(hipFree(b.pool_qvel));
+    b.pool_qvel = nullptr;
+    b.pool_cap = b.pool_n = 0;
+  }
+  if (count == 0) return;
+  const Model& m = *b.model;
+  HIP_CHECK(hipMalloc(&b.pool_qpos, static_cast<size_t>(count) * std::max(1, m.nq) * sizeof(float)));
+  HIP_CHECK(hipMalloc(&b.pool_qvel, static_cast<size_t>(count) * std::max(1, m.nv) * sizeof(float)));
+  b.pool_cap = count;
+}
+
 }  // namespace
 
 BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_contacts) {
@@ -2288,6 +2398,7 @@ BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_cont
     b->st.cam_xpos = static_cast<float*>(dalloc(*b, n * std::max(1, m.ncam) * 3 * sizeof(float)));
     b->st.cam_xmat = static_cast<float*>(dalloc(*b, n * std::max(1, m.ncam) * 9 * sizeof(float)));
     batch_reset(b, -1, 0, n_envs);
+    upload_start_table(*b);
     if (b->dm.rf_mode == 2) {
       // static ray hits: one forward-only pass of env 0 with the producer's model copy
       DevModel prod = b->dm;
@@ -2321,6 +2432,8 @@ void batch_free(BatchImpl* b) {
   if (b->stream) (void)hipStreamSynchronize(b->stream);
   if (b->rstream) (void)hipStreamSynchronize(b->rstream);
   for (void* p : b->allocs) (void)hipFree(p);
+  if (b->pool_qpos) (void)hipFree(b->pool_qpos);
+  if (b->pool_qvel) (void)hipFree(b->pool_qvel);
   if (b->rast_list) (void)hipFree(b->rast_list);
   if (b->snap_ev) (void)hipEventDestroy(b->snap_ev);
   if (b->rend_ev) (void)hipEventDestroy(b->rend_ev);
@@ -2379,6 +2492,78 @@ void batch_reset(BatchImpl* b, int key, int env0, int n) {
     HIP_CHECK(hipMemsetAsync(b->st.xfrc_applied + env0 * row, 0, n * row * sizeof(float), b->stream));
     HIP_CHECK(hipStreamSynchronize(b->stream));
   }
+}
+
+// ---- start-state pool and masked reset (no reference counterpart: the reference resets one mjData
+// on the host).  The pool rows are copied as given, as mj_resetDataKeyframe copies a keyframe.
+void batch_set_start_states(BatchImpl* b, const double* qpos, const double* qvel, int count) {
+  const Model& m = *b->model;
+  if (count > 0 && !qpos) throw std::invalid_argument("null start-state qpos");
+  reserve_pool(*b, count);
+  b->pool_n = count;
+  if (count == 0) return;
+  std::vector<float> q(static_cast<size_t>(count) * m.nq), v(static_cast<size_t>(count) * m.nv, 0.0f);
+  for (size_t i = 0; i < q.size(); ++i) q[i] = static_cast<float>(qpos[i]);
+  if (qvel)
+    for (size_t i = 0; i < v.size(); ++i) v[i] = static_cast<float>(qvel[i]);
+  if (!q.empty())
+    HIP_CHECK(hipMemcpyAsync(b->pool_qpos, q.data(), q.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+  if (!v.empty())
+    HIP_CHECK(hipMemcpyAsync(b->pool_qvel, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+  HIP_CHECK(hipStreamSynchronize(b->stream));  // (the host rows are read by then)
+}
+
+void batch_set_start_states_device(BatchImpl* b, const float* d_qpos, const float* d_qvel, int count) {
+  const Model& m = *b->model;
+  if (count > 0 && !d_qpos) throw std::invalid_argument("null start-state qpos");
+  reserve_pool(*b, count);
+  b->pool_n = count;
+  if (count == 0) return;
+  const size_t nq = static_cast<size_t>(count) * m.nq * sizeof(float), nv = static_cast<size_t>(count) * m.nv * sizeof(float);
+  if (nq) HIP_CHECK(hipMemcpyAsync(b->pool_qpos, d_qpos, nq, hipMemcpyDeviceToDevice, b->stream));
+  if (nv && d_qvel) HIP_CHECK(hipMemcpyAsync(b->pool_qvel, d_qvel, nv, hipMemcpyDeviceToDevice, b->stream));
+  if (nv && !d_qvel) HIP_CHECK(hipMemsetAsync(b->pool_qvel, 0, nv, b->stream));
+}
+
+int batch_num_start_states(const BatchImpl* b) { return b->pool_n; }
+
+void batch_reset_masked_device(BatchImpl* b, const unsigned char* d_mask, const int* d_key, int key) {
+  const Model& m = *b->model;
+  if (!d_mask) throw std::invalid_argument("null reset mask");
+  if (!d_key && key >= m.nkey + b->pool_n) throw std::invalid_argument("keyframe index out of range");
+  HIP_CHECK(hipSetDevice(b->device));
+  ResetArgs a{};
+  a.mask = d_mask;
+  a.keys = d_key;
+  a.key = key < 0 ? -1 : key;
+  a.n = b->n; a.nq = m.nq; a.nv = m.nv; a.nu = m.nu; a.nx = 6 * m.nbody;
+  a.nkey = m.nkey; a.npool = b->pool_n;
+  a.tab_qpos = b->tab_qpos; a.tab_qvel = b->tab_qvel; a.tab_ctrl = b->tab_ctrl; a.tab_time = b->tab_time;
+  a.pool_qpos = b->pool_qpos; a.pool_qvel = b->pool_qvel;
+  a.qpos = b->st.qpos; a.qvel = b->st.qvel;
+  // a bound ctrl buffer is the caller's (a policy's output): it stays bound and unwritten, and so does
+  // st.ctrl, which no launch reads while the binding lasts
+  a.ctrl = b->ctrl_bound ? nullptr : b->st.ctrl;
+  a.qfrc_applied = b->st.qfrc_applied; a.qacc_ws = b->st.qacc_ws;
+  a.xfrc = b->st.xfrc_applied;  // (null until the field is first used: nothing to zero, none made)
+  a.time = b->st.time;
+  a.warning = b->st.warning;
+  const unsigned blocks = static_cast<unsigned>((static_cast<size_t>(b->n) + 15) / 16);  // 16 envs per workgroup
+  hipLaunchKernelGGL(reset_masked_kernel, dim3(blocks), dim3(256), 0, b->stream, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+void batch_reset_masked(BatchImpl* b, const unsigned char* mask, const int* keys, int key) {
+  if (!mask) throw std::invalid_argument("null reset mask");
+  if (!keys && key >= b->model->nkey + b->pool_n) throw std::invalid_argument("keyframe index out of range");
+  HIP_CHECK(hipSetDevice(b->device));
+  const size_t n = static_cast<size_t>(b->n);
+  if (!b->mask_stage) b->mask_stage = static_cast<unsigned char*>(dalloc(*b, n));
+  if (keys && !b->key_stage) b->key_stage = static_cast<int*>(dalloc(*b, n * sizeof(int)));
+  HIP_CHECK(hipMemcpyAsync(b->mask_stage, mask, n, hipMemcpyHostToDevice, b->stream));
+  if (keys) HIP_CHECK(hipMemcpyAsync(b->key_stage, keys, n * sizeof(int), hipMemcpyHostToDevice, b->stream));
+  HIP_CHECK(hipStreamSynchronize(b->stream));  // (the host arrays are read by then; the kernel is not waited for)
+  batch_reset_masked_device(b, b->mask_stage, keys ? b->key_stage : nullptr, key);
 }
 
 void batch_set(BatchImpl* b, int field, const double* host, int env0, int n) {

@@ -206,6 +206,11 @@ def lib() -> C.CDLL:
         L.mrs_batch_num_envs.argtypes = [C.c_void_p]
         L.mrs_batch_set_stream.argtypes = [C.c_void_p, C.c_void_p]
         L.mrs_batch_reset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        L.mrs_batch_set_start_states.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.mrs_batch_set_start_states_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.mrs_batch_num_start_states.argtypes = [C.c_void_p]
+        L.mrs_batch_reset_masked_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.mrs_batch_reset_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.mrs_batch_set_field.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.mrs_batch_get_field.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.mrs_batch_device_ptr.restype = C.c_void_p
@@ -377,6 +382,56 @@ class Batch:
 
     def reset(self, key: int = -1, env0: int = 0, n: int | None = None) -> None:
         _check(lib().mrs_batch_reset(self._h, key, env0, self.n - env0 if n is None else n))
+
+    def set_start_states(self, qpos, qvel=None) -> None:
+        """replace the pool of start states reset_where addresses as nkey + row: qpos [count, nq] and
+        qvel [count, nv] (None: zeros), copied as given; an empty qpos frees the pool"""
+        m = self.model
+        q = np.ascontiguousarray(qpos, dtype=np.float64)
+        count = 0 if q.size == 0 else q.reshape(-1, m.nq).shape[0]
+        v = None
+        if qvel is not None and count:
+            v = np.ascontiguousarray(qvel, dtype=np.float64)
+            if v.size != count * m.nv:
+                raise ValueError(f"qvel must have shape ({count}, {m.nv})")
+        _check(lib().mrs_batch_set_start_states(self._h, q.ctypes.data if count else None,
+                                                 v.ctypes.data if v is not None and v.size else None, count))
+
+    def set_start_states_device(self, qpos_ptr: int, qvel_ptr: int | None, count: int) -> None:
+        """the same from device fp32 buffers [count, nq] / [count, nv] (qvel_ptr 0 or None: zeros),
+        copied device-to-device, asynchronous on the batch stream"""
+        _check(lib().mrs_batch_set_start_states_device(self._h, C.c_void_p(qpos_ptr) if qpos_ptr else None,
+                                                        C.c_void_p(qvel_ptr) if qvel_ptr else None, count))
+
+    @property
+    def num_start_states(self) -> int:
+        return lib().mrs_batch_num_start_states(self._h)
+
+    def reset_where(self, mask, keys=None, key: int = -1) -> None:
+        """reset the envs with mask[e] set (bool or uint8 [n]), each to the start index keys[e]
+        (int32 [n]) or, without keys, to `key`: -1 qpos0, 0 .. nkey-1 a keyframe, nkey + r pool row r.
+        Unmasked envs are not written and a bound ctrl buffer stays bound (mrs_batch_reset_masked)"""
+        mask = np.asarray(mask)
+        if mask.shape != (self.n,):
+            raise ValueError(f"mask must have shape ({self.n},), not {mask.shape}")
+        if mask.dtype not in (np.bool_, np.uint8):
+            raise ValueError(f"mask must be bool or uint8, not {mask.dtype}")
+        mask = np.ascontiguousarray(mask).view(np.uint8)
+        if keys is not None:
+            keys = np.asarray(keys)
+            if keys.shape != (self.n,):
+                raise ValueError(f"keys must have shape ({self.n},), not {keys.shape}")
+            if keys.dtype != np.int32:
+                raise ValueError(f"keys must be int32, not {keys.dtype}")
+            keys = np.ascontiguousarray(keys)
+        _check(lib().mrs_batch_reset_masked(self._h, mask.ctypes.data, keys.ctypes.data if keys is not None else None,
+                                             key))
+
+    def reset_where_device(self, mask_ptr: int, keys_ptr: int = 0, key: int = -1) -> None:
+        """the same from device buffers (a torch.bool / uint8 mask and an int32 key tensor's data_ptr()):
+        one launch on the batch stream, no host synchronisation"""
+        _check(lib().mrs_batch_reset_masked_device(self._h, C.c_void_p(mask_ptr) if mask_ptr else None,
+                                                    C.c_void_p(keys_ptr) if keys_ptr else None, key))
 
     def layout(self) -> dict:
         """kernel configuration of this batch (diagnostics): group width, LDS and scratch floats per
