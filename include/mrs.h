@@ -163,6 +163,16 @@ int mrs_batch_bind_ctrl_device(mrs_batch* b, const float* d_ctrl);
  * stream takes effect at the next step / forward launch; like ctrl / qfrc_applied the wrenches are held
  * over the n steps of a launch (and RK4's stages), mrs_batch_reset zeroes the reset envs' rows, and the
  * NaN auto-reset keeps them. */
+/* mjData.act: the activations of the model's na stateful actuators (dyntype integrator, filter or
+ * filterexact; mrs_model_view actuator_actadr gives each one's column).  Integrated state like qpos
+ * and qvel: a step launch loads it, advances it every step and stores it back; every reset writes it
+ * (a keyframe's key_act, else 0) and the NaN auto-reset zeroes it.  Not an MRS_FIELD_* value: host
+ * layout [n][na] fp64 for envs [env0, env0+n); with na == 0 set / get succeed and copy nothing. */
+int mrs_batch_set_act(mrs_batch* b, const double* host, int env0, int n);
+int mrs_batch_get_act(mrs_batch* b, double* host, int env0, int n);
+/* device pointer of the activations, [n_envs][na] fp32; accesses ordered on the batch stream see the
+ * launches' values.  NULL when na == 0. */
+float* mrs_batch_act_device_ptr(mrs_batch* b);
 
 /* replaces mj_step (src/mujoco_system_interface.cpp:1691,1731): advance every env n_steps times,
  * fused in one launch; ctrl / qfrc_applied are held constant (zero-order hold) across the n steps,

@@ -38,7 +38,7 @@ enum { MRS_BUILTIN_NONE = 0, MRS_BUILTIN_GRADIENT = 1, MRS_BUILTIN_CHECKER = 2, 
 enum { MRS_MARK_NONE = 0, MRS_MARK_EDGE = 1, MRS_MARK_CROSS = 2 };
 #define MRS_NEQDATA 11
 enum { MRS_TRN_JOINT = 0, MRS_TRN_TENDON = 3 };
-enum { MRS_DYN_NONE = 0 };
+enum { MRS_DYN_NONE = 0, MRS_DYN_INTEGRATOR = 1, MRS_DYN_FILTER = 2, MRS_DYN_FILTEREXACT = 3 };
 enum { MRS_GAIN_FIXED = 0, MRS_GAIN_AFFINE = 1 };
 enum { MRS_BIAS_NONE = 0, MRS_BIAS_AFFINE = 1 };
 enum { MRS_OBJ_UNKNOWN = 0, MRS_OBJ_BODY = 1, MRS_OBJ_JOINT = 3, MRS_OBJ_GEOM = 5, MRS_OBJ_SITE = 6,
@@ -204,6 +204,14 @@ typedef struct mrs_model_view {
    * box): the zone of a touch sensor */
   const int *site_type;
   const double *site_size /*3*/;
+
+  /* activation state (mjModel na / actuator_act* / actuator_dynprm, mjData.act): na counts the
+   * actuators with dyntype != MRS_DYN_NONE, one activation each; actuator_actadr is the actuator's
+   * address in act (-1: stateless; stateful and stateless actuators interleave), actuator_actnum 0 or
+   * 1.  dynprm[0] is the filters' time constant.  actlimited clamps the activation to actrange after
+   * every advance; actearly: the force uses the next activation.  key_act [nkey][na]. */
+  const int *actuator_actadr, *actuator_actnum, *actuator_actlimited, *actuator_actearly;
+  const double *actuator_dynprm /*3*/, *actuator_actrange /*2*/, *key_act;
 } mrs_model_view;
 
 #ifdef __cplusplus

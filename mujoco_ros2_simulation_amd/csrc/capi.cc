@@ -261,6 +261,22 @@ int mrs_batch_bind_ctrl_device(mrs_batch* b, const float* d_ctrl) {
   });
 }
 
+int mrs_batch_set_act(mrs_batch* b, const double* host, int env0, int n) {
+  return guarded([&] {
+    if (!b || !host) throw std::invalid_argument("null argument");
+    mrs::batch_set_act(b->impl, host, env0, n);
+  });
+}
+
+int mrs_batch_get_act(mrs_batch* b, double* host, int env0, int n) {
+  return guarded([&] {
+    if (!b || !host) throw std::invalid_argument("null argument");
+    mrs::batch_get_act(b->impl, host, env0, n);
+  });
+}
+
+float* mrs_batch_act_device_ptr(mrs_batch* b) { return b ? mrs::batch_act_device_ptr(b->impl) : nullptr; }
+
 int mrs_batch_step(mrs_batch* b, int n_steps) {
   return guarded([&] {
     if (!b) throw std::invalid_argument("null batch");

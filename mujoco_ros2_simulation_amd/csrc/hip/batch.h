@@ -27,6 +27,10 @@ void batch_reset_masked(BatchImpl* b, const unsigned char* mask, const int* keys
 void batch_set(BatchImpl* b, int field, const double* host, int env0, int n);
 void batch_get(BatchImpl* b, int field, double* host, int env0, int n);
 void* batch_device_ptr(BatchImpl* b, int field);
+// the activations [n][na] (mjData.act; no MRS_FIELD_* value of their own)
+void batch_set_act(BatchImpl* b, const double* host, int env0, int n);
+void batch_get_act(BatchImpl* b, double* host, int env0, int n);
+float* batch_act_device_ptr(BatchImpl* b);  // null when na == 0
 void batch_set_ctrl_device(BatchImpl* b, const float* d_ctrl);
 void batch_bind_ctrl_device(BatchImpl* b, const float* d_ctrl);  // zero-copy ctrl source (null: own buffer)
 void batch_set_timing(BatchImpl* b, int mask);  // launches timed for batch_last_kernel_ms (bit 0 step, 1 frames)

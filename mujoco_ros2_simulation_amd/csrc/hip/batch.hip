@@ -881,11 +881,12 @@ __global__ __launch_bounds__(256) void depth_kernel_mesh(const int* geom_type, c
 struct ResetArgs {
   const unsigned char* mask;  // [n]
   const int* keys;            // [n] start indices, or null: `key` for every env
-  int key, n, nq, nv, nu, nx, nkey, npool;
-  const float *tab_qpos, *tab_qvel, *tab_ctrl;  // [1 + nkey][nq | nv | nu]
+  int key, n, nq, nv, nu, na, nx, nkey, npool;
+  const float *tab_qpos, *tab_qvel, *tab_ctrl, *tab_act;  // [1 + nkey][nq | nv | nu | na]
   const double* tab_time;                       // [1 + nkey]
   const float *pool_qpos, *pool_qvel;           // [npool][nq | nv]
   float *qpos, *qvel, *ctrl, *qfrc_applied, *qacc_ws, *xfrc;  // ctrl / xfrc null: not written
+  float* act;  // [n][na] (null when na == 0)
   double* time;
   int* warning;
 };
@@ -895,13 +896,14 @@ __global__ __launch_bounds__(256) void reset_masked_kernel(const ResetArgs a) {
   if (e >= static_cast<size_t>(a.n) || !a.mask[e]) return;
   int k = a.keys ? a.keys[e] : a.key;
   if (k < -1 || k >= a.nkey + a.npool) k = -1;  // (an index outside the table and the pool: qpos0)
-  const float *sq, *sv, *sc = nullptr;  // (a pool row has no ctrl: zeros)
+  const float *sq, *sv, *sc = nullptr, *sa = nullptr;  // (a pool row has no ctrl and no act: zeros)
   double t = 0;
   if (k < a.nkey) {
     const size_t row = static_cast<size_t>(k + 1);
     sq = a.tab_qpos + row * a.nq;
     sv = a.tab_qvel + row * a.nv;
     sc = a.tab_ctrl + row * a.nu;
+    sa = a.tab_act + row * a.na;
     t = a.tab_time[row];
   } else {
     const size_t row = static_cast<size_t>(k - a.nkey);
@@ -918,6 +920,7 @@ __global__ __launch_bounds__(256) void reset_masked_kernel(const ResetArgs a) {
     for (int i = lane; i < a.nu; i += 16) a.ctrl[e * a.nu + i] = sc ? sc[i] : 0.0f;
   if (a.xfrc)
     for (int i = lane; i < a.nx; i += 16) a.xfrc[e * a.nx + i] = 0;
+  for (int i = lane; i < a.na; i += 16) a.act[e * a.na + i] = sa ? sa[i] : 0.0f;
   if (lane < 4) a.warning[e * 4 + lane] = 0;
   if (lane == 4) a.time[e] = t;
 }
@@ -966,7 +969,7 @@ struct BatchImpl {
   // start states of the masked reset (reset_masked_kernel), fp32 in the state fields' layout: the
   // model's table [1 + nkey] (row 0 qpos0 with zero qvel / ctrl / time, row 1 + k keyframe k; made at
   // batch creation) and the runtime pool [pool_n] of batch_set_start_states (capacity pool_cap rows)
-  float *tab_qpos = nullptr, *tab_qvel = nullptr, *tab_ctrl = nullptr;
+  float *tab_qpos = nullptr, *tab_qvel = nullptr, *tab_ctrl = nullptr, *tab_act = nullptr;
   double* tab_time = nullptr;
   float *pool_qpos = nullptr, *pool_qvel = nullptr;
   int pool_n = 0, pool_cap = 0;
@@ -1144,6 +1147,7 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
     if (t == MRS_SENS_FRAMELINACC) d.acc_sens |= 1;  // reads cacc
     if (t == MRS_SENS_TOUCH) d.acc_sens |= 2;        // reads the row forces
   }
+  d.na = m.na;
   d.nq = m.nq; d.nv = m.nv; d.nu = m.nu; d.nbody = m.nbody; d.njnt = m.njnt; d.ngeom = m.ngeom;
   d.nsite = m.nsite; d.ncam = m.ncam; d.nsensor = m.nsensor; d.nsensordata = m.nsensordata;
   d.max_depth = m.max_depth;
@@ -1624,6 +1628,23 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
     }
   }
   P.addf(&d.actrec, actrec);
+  // activation dynamics of the stateful actuators (step.hip act_input / act_next), read only when
+  // na > 0: per actuator (8 floats) dyntype, address in act (-1 stateless), the time constant
+  // max(tau, 1e-15), filterexact's step factor tau (1 - exp(-h / tau)) from fp64, the activation limit
+  // flag and range, actearly
+  std::vector<float> actdyn;
+  if (m.na > 0) {
+    auto fbits = [](int v) { float f; std::memcpy(&f, &v, sizeof f); return f; };
+    for (int a = 0; a < m.nu; ++a) {
+      const double tau = std::max(m.actuator_dynprm[3 * a], 1e-15);
+      const std::vector<float> r = {fbits(m.actuator_dyntype[a]), fbits(m.actuator_actadr[a]), static_cast<float>(tau),
+                                    static_cast<float>(tau * -std::expm1(-m.timestep / tau)),
+                                    fbits(m.actuator_actlimited[a]), static_cast<float>(m.actuator_actrange[2 * a]),
+                                    static_cast<float>(m.actuator_actrange[2 * a + 1]), fbits(m.actuator_actearly[a])};
+      actdyn.insert(actdyn.end(), r.begin(), r.end());
+    }
+  }
+  P.addf(&d.actdyn, actdyn);
   P.addf(&d.dofrec, dofrec);
   // tree tables for the smooth dynamics (step.hip com_pos, make_M, com_vel, rne), staged in workgroup
   // LDS: per body (8 floats) mass, subtree mass, root, parent, subtree end, dof address, dof count,
@@ -1974,6 +1995,7 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
     L.H = blocked && m.solver != MRS_SOL_PGS ? take(nv * nv) : 0;
     L.Li = blocked && m.solver == MRS_SOL_PGS ? take(std::max(1, d.nMblk)) : 0;
     L.rk = m.integrator == MRS_INT_RK4 ? take(std::max(1, m.nq) + 4 * nv) : 0;
+    L.act = m.na > 0 ? take(4 * m.na) : 0;
     L.total = off;
   };
   lds_layout(false);
@@ -2302,7 +2324,7 @@ void* field_ptr(BatchImpl& b, int field) {
 void upload_start_table(BatchImpl& b) {
   const Model& m = *b.model;
   const size_t rows = static_cast<size_t>(m.nkey) + 1;
-  std::vector<float> q(rows * m.nq), v(rows * m.nv, 0.0f), c(rows * m.nu, 0.0f);
+  std::vector<float> q(rows * m.nq), v(rows * m.nv, 0.0f), c(rows * m.nu, 0.0f), a(rows * m.na, 0.0f);
   std::vector<double> t(rows, 0.0);
   for (int i = 0; i < m.nq; ++i) q[i] = static_cast<float>(m.qpos0[i]);
   for (int k = 0; k < m.nkey; ++k) {
@@ -2310,11 +2332,13 @@ void upload_start_table(BatchImpl& b) {
     for (int i = 0; i < m.nq; ++i) q[r * m.nq + i] = static_cast<float>(m.key_qpos[s * m.nq + i]);
     for (int i = 0; i < m.nv; ++i) v[r * m.nv + i] = static_cast<float>(m.key_qvel[s * m.nv + i]);
     for (int i = 0; i < m.nu; ++i) c[r * m.nu + i] = static_cast<float>(m.key_ctrl[s * m.nu + i]);
+    for (int i = 0; i < m.na; ++i) a[r * m.na + i] = static_cast<float>(m.key_act[s * m.na + i]);
     t[r] = m.key_time[k];
   }
   b.tab_qpos = static_cast<float*>(dalloc(b, q.size() * sizeof(float)));
   b.tab_qvel = static_cast<float*>(dalloc(b, v.size() * sizeof(float)));
   b.tab_ctrl = static_cast<float*>(dalloc(b, c.size() * sizeof(float)));
+  b.tab_act = static_cast<float*>(dalloc(b, a.size() * sizeof(float)));
   b.tab_time = static_cast<double*>(dalloc(b, t.size() * sizeof(double)));
   auto put = [&](void* dst, const void* src, size_t bytes) {
     if (bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, b.stream));
@@ -2322,6 +2346,7 @@ void upload_start_table(BatchImpl& b) {
   put(b.tab_qpos, q.data(), q.size() * sizeof(float));
   put(b.tab_qvel, v.data(), v.size() * sizeof(float));
   put(b.tab_ctrl, c.data(), c.size() * sizeof(float));
+  put(b.tab_act, a.data(), a.size() * sizeof(float));
   put(b.tab_time, t.data(), t.size() * sizeof(double));
   HIP_CHECK(hipStreamSynchronize(b.stream));
 }
@@ -2374,6 +2399,7 @@ BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_cont
     b->st.qacc = static_cast<float*>(dalloc(*b, n * std::max(1, m.nv) * sizeof(float)));
     b->st.qfrc_act = static_cast<float*>(dalloc(*b, n * std::max(1, m.nv) * sizeof(float)));
     b->st.sensordata = static_cast<float*>(dalloc(*b, n * std::max(1, m.nsensordata) * sizeof(float)));
+    b->st.act = m.na > 0 ? static_cast<float*>(dalloc(*b, n * m.na * sizeof(float))) : nullptr;
     b->st.time = static_cast<double*>(dalloc(*b, n * sizeof(double)));
     b->st.warning = static_cast<int*>(dalloc(*b, n * 4 * sizeof(int)));
     b->st.ncon = static_cast<int*>(dalloc(*b, n * sizeof(int)));
@@ -2485,6 +2511,14 @@ void batch_reset(BatchImpl* b, int key, int env0, int n) {
   batch_set(b, MRS_FIELD_QFRC_APPLIED, zeros.data(), env0, n);
   batch_set(b, MRS_FIELD_QACC_WARMSTART, zeros.data(), env0, n);
   batch_set(b, MRS_FIELD_TIME, t.data(), env0, n);
+  if (m.na > 0) {  // (mj_resetData zeroes act; mj_resetDataKeyframe copies key_act)
+    std::vector<double> act(static_cast<size_t>(n) * m.na, 0.0);
+    if (key >= 0)
+      for (int e = 0; e < n; ++e)
+        std::copy(&m.key_act[static_cast<size_t>(key) * m.na], &m.key_act[static_cast<size_t>(key) * m.na] + m.na,
+                  &act[static_cast<size_t>(e) * m.na]);
+    batch_set_act(b, act.data(), env0, n);
+  }
   std::vector<double> w(static_cast<size_t>(n) * 4, 0.0);
   batch_set(b, MRS_FIELD_WARNING, w.data(), env0, n);
   if (b->st.xfrc_applied) {  // (mj_resetData zeroes xfrc_applied)
@@ -2536,11 +2570,11 @@ void batch_reset_masked_device(BatchImpl* b, const unsigned char* d_mask, const 
   a.mask = d_mask;
   a.keys = d_key;
   a.key = key < 0 ? -1 : key;
-  a.n = b->n; a.nq = m.nq; a.nv = m.nv; a.nu = m.nu; a.nx = 6 * m.nbody;
+  a.n = b->n; a.nq = m.nq; a.nv = m.nv; a.nu = m.nu; a.na = m.na; a.nx = 6 * m.nbody;
   a.nkey = m.nkey; a.npool = b->pool_n;
-  a.tab_qpos = b->tab_qpos; a.tab_qvel = b->tab_qvel; a.tab_ctrl = b->tab_ctrl; a.tab_time = b->tab_time;
+  a.tab_qpos = b->tab_qpos; a.tab_qvel = b->tab_qvel; a.tab_ctrl = b->tab_ctrl; a.tab_act = b->tab_act; a.tab_time = b->tab_time;
   a.pool_qpos = b->pool_qpos; a.pool_qvel = b->pool_qvel;
-  a.qpos = b->st.qpos; a.qvel = b->st.qvel;
+  a.qpos = b->st.qpos; a.qvel = b->st.qvel; a.act = b->st.act;
   // a bound ctrl buffer is the caller's (a policy's output): it stays bound and unwritten, and so does
   // st.ctrl, which no launch reads while the binding lasts
   a.ctrl = b->ctrl_bound ? nullptr : b->st.ctrl;
@@ -2629,6 +2663,34 @@ void batch_get(BatchImpl* b, int field, double* host, int env0, int n) {
 }
 
 void* batch_device_ptr(BatchImpl* b, int field) { return field_ptr(*b, field); }
+
+void batch_set_act(BatchImpl* b, const double* host, int env0, int n) {
+  const int na = b->model->na;
+  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
+  if (n == 0 || na == 0) return;
+  HIP_CHECK(hipSetDevice(b->device));
+  const size_t cnt = static_cast<size_t>(n) * na;
+  std::vector<float> tmp(cnt);
+  for (size_t i = 0; i < cnt; ++i) tmp[i] = static_cast<float>(host[i]);
+  HIP_CHECK(hipMemcpyAsync(b->st.act + static_cast<size_t>(env0) * na, tmp.data(), cnt * sizeof(float),
+                           hipMemcpyHostToDevice, b->stream));
+  HIP_CHECK(hipStreamSynchronize(b->stream));
+}
+
+void batch_get_act(BatchImpl* b, double* host, int env0, int n) {
+  const int na = b->model->na;
+  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
+  if (n == 0 || na == 0) return;
+  HIP_CHECK(hipSetDevice(b->device));
+  const size_t cnt = static_cast<size_t>(n) * na;
+  std::vector<float> tmp(cnt);
+  HIP_CHECK(hipMemcpyAsync(tmp.data(), b->st.act + static_cast<size_t>(env0) * na, cnt * sizeof(float),
+                           hipMemcpyDeviceToHost, b->stream));
+  HIP_CHECK(hipStreamSynchronize(b->stream));
+  for (size_t i = 0; i < cnt; ++i) host[i] = tmp[i];
+}
+
+float* batch_act_device_ptr(BatchImpl* b) { return b->st.act; }
 
 void batch_bind_ctrl_device(BatchImpl* b, const float* d_ctrl) { b->ctrl_bound = d_ctrl; }
 

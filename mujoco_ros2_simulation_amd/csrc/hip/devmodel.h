@@ -49,7 +49,9 @@ struct LdsLayout {
                // the stage velocities and accelerations [nv each]
       niter,   // constraint solver iterations of the last forward (int bits)
       hcon,    // helper waves: the step's contact and row counts from the helper (int bits)
-      Lh;      // helper waves: the factor of M + h D for the integrator, built by the helper (0: none)
+      Lh,      // helper waves: the factor of M + h D for the integrator, built by the helper (0: none)
+      act;     // models with stateful actuators (na > 0): act [na], act_dot [na], and RK4's initial act and
+               // B-weighted sum of the stages' act_dot [na each]
   int total;  // floats per env (multiple of 4)
 };
 
@@ -227,6 +229,11 @@ struct DevModel {
   // wrenches is on this copy, a scalar load beside the phase's other model fields.  Plain global
   // memory [n_envs][nbody][6], read once per forward pass
   const float* xfrc;
+  // stateful actuators (mjData.act): their count -- 0 for every model without
+  // actuator dynamics, whose launches then take none of the activation code -- and the per-actuator
+  // dynamics records (batch.hip actdyn, 8 floats each; packed only when na > 0)
+  int na;
+  CPtr<float> actdyn;
 };
 constexpr int kRayBlock = 128;
 
@@ -260,6 +267,7 @@ struct DevState {
   // [n_envs][nbody][6] per-body Cartesian wrenches (mjData.xfrc_applied: world-frame force, then
   // torque, at the body's centre of mass); null until the field is first used (batch.hip ensure_xfrc)
   float* xfrc_applied;
+  float* act;  // [n_envs][na] activations of the stateful actuators (mjData.act); null when na == 0
   float* geom_xpos;  // [n_envs][ngeom][3]  kinematics of the last forward (for the depth camera)
   float* geom_xmat;  // [n_envs][ngeom][9]
   float* cam_xpos;   // [n_envs][ncam][3]

@@ -2653,6 +2653,79 @@ __device__ float xfrc_qfrc(ENV_PARAMS) {
   return q;
 }
 
+// ---- stateful actuators (mjData.act).  Everything here is out of line and reached
+// only behind the scalar test m.na > 0, so a model without actuator dynamics pays that branch alone.
+// The records are batch.hip's actdyn (8 floats per actuator), the state L.act [na] with act_dot behind it.
+
+// mj_nextActivation: filterexact act + act_dot * tau (1 - exp(-h / tau)) (the factor from the host, in
+// fp64), integrator / filter act + h act_dot, then the clamp to actrange
+__device__ __forceinline__ float act_next(const CPtr<float> dr, float act, float act_dot, float h) {
+  float x = __float_as_int(dr[0]) == MRS_DYN_FILTEREXACT ? act + act_dot * dr[3] : act + h * act_dot;
+  if (__float_as_int(dr[4])) x = clampf(x, dr[5], dr[6]);
+  return x;
+}
+// mj_fwdActuation's activation part for actuator a (ctrl already clamped): act_dot into its slot, and
+// the value that takes ctrl's place in gain * x + bias -- the activation, or with actearly the next
+// one; a stateless actuator keeps ctrl
+template <int G>
+__device__ float act_input(ENV_PARAMS, int a, float ctrl) {
+  ENV_UNPACK;
+  const CPtr<float> dr = m.actdyn + 8 * a;
+  const int adr = __float_as_int(dr[1]);
+  if (adr < 0) return ctrl;
+  const float act = s[L.act + adr];
+  const float dot = __float_as_int(dr[0]) == MRS_DYN_INTEGRATOR ? ctrl : (ctrl - act) / dr[2];
+  s[L.act + m.na + adr] = dot;
+  return __float_as_int(dr[7]) ? act_next(dr, act, dot, m.timestep) : act;
+}
+// the input of actuator a's velocity derivative (mjd_smooth_vel: gain_vel * act, the current
+// activation also under actearly)
+template <int G>
+__device__ float act_state(ENV_PARAMS, int a, float ctrl) {
+  ENV_UNPACK;
+  const int adr = __float_as_int(m.actdyn[8 * a + 1]);
+  return adr < 0 ? ctrl : s[L.act + adr];
+}
+// mj_advance's activation part (Euler, implicitfast, implicit), lane per actuator
+template <int G>
+__device__ void act_advance(ENV_PARAMS) {
+  ENV_UNPACK;
+  #pragma unroll 1
+  for (int a = lane; a < m.nu; a += G) {
+    const CPtr<float> dr = m.actdyn + 8 * a;
+    const int adr = __float_as_int(dr[1]);
+    if (adr < 0) continue;
+    s[L.act + adr] = act_next(dr, s[L.act + adr], s[L.act + m.na + adr], m.timestep);
+  }
+  wsync();
+}
+// mj_RungeKutta's activation part beside rk4_stage (stage 1..3) and rk4_final (stage 4): the stage
+// states act0 + h A_i act_dot_{i-1} unclamped, the final one mj_nextActivation(act0, sum B_j act_dot_j)
+template <int G>
+__device__ void rk4_act(ENV_PARAMS, int stage) {
+  ENV_UNPACK;
+  const float h = m.timestep;
+  const float A = stage == 3 ? 1.0f : 0.5f;
+  const float B = stage == 1 || stage == 4 ? 1.0f / 6 : 1.0f / 3;
+  lfloat* act = s + L.act;
+  lfloat *dot = act + m.na, *a0 = dot + m.na, *sum = a0 + m.na;
+  #pragma unroll 1
+  for (int a = lane; a < m.nu; a += G) {
+    const CPtr<float> dr = m.actdyn + 8 * a;
+    const int adr = __float_as_int(dr[1]);
+    if (adr < 0) continue;
+    const float d = dot[adr];
+    if (stage == 1) {
+      a0[adr] = act[adr];
+      sum[adr] = B * d;
+    } else {
+      sum[adr] += B * d;
+    }
+    act[adr] = stage == 4 ? act_next(dr, a0[adr], sum[adr], h) : a0[adr] + h * (A * d);
+  }
+  wsync();
+}
+
 // mj_passive + mj_fwdActuation + qfrc_smooth + qacc_smooth (lane per dof)
 template <int G>
 __device__ MRS_PHASE float smooth_forces(ENV_PARAMS) {
@@ -2686,6 +2759,8 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS) {
       const float vel = gear * (dad >= 0 ? s[L.qvel + dad] : s[L.ten + 2 * (-1 - dad) + 1]);
       float ctrl = s[L.ctrl + a];
       if (__float_as_int(ar[3]) && !(m.disableflags & MRS_DSBL_CLAMPCTRL)) ctrl = clampf(ctrl, ar[4], ar[5]);
+      // a stateful actuator: its activation (with actearly the next one) takes ctrl's place
+      if (m.na > 0) { [[clang::noinline]] ctrl = act_input<G>(ENV_ARGS, a, ctrl); }
       float gain = __float_as_int(ar[6]) == MRS_GAIN_AFFINE ? ar[7] + ar[8] * len + ar[9] * vel : ar[7];
       float bias = __float_as_int(ar[10]) == MRS_BIAS_AFFINE ? ar[11] + ar[12] * len + ar[13] * vel : 0.0f;
       force = gain * ctrl + bias;
@@ -7346,6 +7421,8 @@ __device__ MRS_PHASE void reset_env(ENV_PARAMS) {
   for (int i = lane; i < m.nq; i += G) s[L.qpos + i] = m.qpos0[i];
   #pragma unroll 1
   for (int i = lane; i < m.nv; i += G) { s[L.qvel + i] = 0; s[L.qacc_ws + i] = 0; }
+  #pragma unroll 1
+  for (int i = lane; i < m.na; i += G) s[L.act + i] = 0;
   wsync();
 }
 
@@ -7501,6 +7578,7 @@ __device__ __forceinline__ float integrate_dg(ENV_PARAMS) {
           const float gv = __float_as_int(ar[6]) == MRS_GAIN_AFFINE ? ar[9] : 0.0f;
           float ctrl = s[L.ctrl + a];
           if (__float_as_int(ar[3]) && !(m.disableflags & MRS_DSBL_CLAMPCTRL)) ctrl = clampf(ctrl, ar[4], ar[5]);
+          if (m.na > 0) { [[clang::noinline]] ctrl = act_state<G>(ENV_ARGS, a, ctrl); }
           const float g = ar[2];
           dg -= g * g * (bv + gv * ctrl);
         };
@@ -7590,7 +7668,7 @@ __device__ MRS_PHASE void integrate(ENV_PARAMS, bool prefac = false) {
 // the velocity derivative of the actuators and passive forces on lane j's dof, as integrate()'s
 // implicitfast path (minus the derivative of qfrc_passive + qfrc_actuator)
 template <int G>
-__device__ __forceinline__ float implicit_dg(const DevModel& m, const lfloat* s, int lane) {
+__device__ __forceinline__ float implicit_dg(const DevModel* mp, const DevModel& m, const lfloat* s, int lane) {
   const LdsLayout& L = m.L;
   const auto dr = dof_tab<G>(m, lane);
   float dg = (m.disableflags & MRS_DSBL_PASSIVE) ? 0.0f : dr[9];
@@ -7605,6 +7683,7 @@ __device__ __forceinline__ float implicit_dg(const DevModel& m, const lfloat* s,
       const float gv = __float_as_int(ar[6]) == MRS_GAIN_AFFINE ? ar[9] : 0.0f;
       float ctrl = s[L.ctrl + a];
       if (__float_as_int(ar[3]) && !(m.disableflags & MRS_DSBL_CLAMPCTRL)) ctrl = clampf(ctrl, ar[4], ar[5]);
+      if (m.na > 0) { [[clang::noinline]] ctrl = act_state<G>(mp, (lfloat*)s, nullptr, lane, a, ctrl); }
       const float g = ar[2];
       dg -= g * g * (bv + gv * ctrl);
     };
@@ -7637,7 +7716,7 @@ __device__ void integrate_implicit(ENV_PARAMS) {
   const int nv = m.nv;
   const float h = m.timestep;
   const float qacc = lane < nv ? s[L.qacc + lane] : 0.0f;
-  const float dg = lane < nv ? implicit_dg<G>(m, s, lane) : 0.0f;
+  const float dg = lane < nv ? implicit_dg<G>(mp, m, s, lane) : 0.0f;
   const float rhs = lane < nv ? s[L.qfrc_smooth + lane] + s[L.qfrc_con + lane] : 0.0f;
   int ta = 0, tn = nv, tmax = nv;
   if constexpr (G == 64) {
@@ -7823,6 +7902,12 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
   }
   #pragma unroll 1
   for (int i = lane; i < (is_helper ? 0 : m.nu); i += G) s[L.ctrl + i] = st.ctrl[e * m.nu + i];
+  // the activations, and act_dot zero until a forward pass writes it (MRS_DSBL_ACTUATION: never)
+  #pragma unroll 1
+  for (int i = lane; i < (is_helper ? 0 : m.na); i += G) {
+    s[L.act + i] = st.act[e * m.na + i];
+    s[L.act + m.na + i] = 0;
+  }
   // xfrc_applied in use: the group's row of it for the phases (xfrc_row) -- a mirror group reads its
   // primary's env, a group past n_envs none
   if (st.xfrc_applied && lane == 0 && !is_helper) scr[m.S.xfrc] = __int_as_float(env < n_envs ? env : -1);
@@ -7969,15 +8054,18 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
       // stages out of line (RK4 models only), each followed by a forward without sensors
       #pragma unroll 1
       for (int stage = 1; stage < 4; ++stage) {
+        if (m.na > 0) { [[clang::noinline]] rk4_act<G>(ENV_ARGS, stage); }
         [[clang::noinline]] rk4_stage<G>(ENV_ARGS, stage);
         [[clang::noinline]] ncon = forward<G, kPrimal>(ENV_ARGS, nullptr, false PH_ACC_ARG);
       }
+      if (m.na > 0) { [[clang::noinline]] rk4_act<G>(ENV_ARGS, 4); }
       [[clang::noinline]] rk4_final<G>(ENV_ARGS);
     } else {
       PH_BEGIN();
       // (a re-run step's factor is its own: the helper's was of the first forward's state)
       MRS_CALL(G, integrate<G>(ENV_ARGS, (helpers && L.Lh != 0 && !__any(redo)) || (G == 16 && m.fuse_ih)));
       PH_END(ph_acc, PH_INTEG);
+      if (m.na > 0) { [[clang::noinline]] act_advance<G>(ENV_ARGS); }
     }
     time += m.timestep_d;
   }
@@ -8013,6 +8101,8 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
     st.qacc[e * m.nv + i] = s[L.qacc + i];
     st.qfrc_act[e * m.nv + i] = s[L.qfrc_act + i];
   }
+  #pragma unroll 1
+  for (int i = lane; i < m.na; i += G) st.act[e * m.na + i] = s[L.act + i];
   if (lane == 0) {
     st.time[e] = time;
     st.ncon[e] = ncon;

@@ -1088,7 +1088,7 @@ struct Compiler {
     for (auto& cp : sec->children) {
       const XmlElement* e = cp.get();
       const std::string& tag = e->tag;
-      if (tag != "motor" && tag != "position" && tag != "velocity" && tag != "general")
+      if (tag != "motor" && tag != "position" && tag != "velocity" && tag != "general" && tag != "intvelocity")
         fail(e, "unsupported actuator type");
       const DefaultClass* cls = resolve_class(e, "");
       std::string joint, tendon;
@@ -1112,9 +1112,21 @@ struct Compiler {
       int ctrllimited = get_tristate(e, cls, tag, "ctrllimited");
       int forcelimited = get_tristate(e, cls, tag, "forcelimited");
       int gaintype = MRS_GAIN_FIXED, biastype = MRS_BIAS_NONE;
+      // activation dynamics (mjtDyn; dynprm[0] is the time constant of the filters)
+      int dyntype = MRS_DYN_NONE, actearly = 0;
+      double dynprm[3] = {1, 0, 0}, actrange[2] = {0, 0};
+      bool has_actrange = get_reals(e, cls, tag, "actrange", actrange, 2, true);
+      int actlimited = get_tristate(e, cls, tag, "actlimited");
+      {
+        std::string s;
+        if (get_str(e, cls, tag, "actearly", s)) {
+          if (s != "true" && s != "false") fail(e, "attribute 'actearly' must be true/false");
+          actearly = s == "true";
+        }
+      }
       if (tag == "motor") {
         gain[0] = 1;
-      } else if (tag == "position") {
+      } else if (tag == "position" || tag == "intvelocity") {
         double kp = 1, kv = 0, dampratio = 0;
         get_real(e, cls, tag, "kp", kp);
         bool has_kv = get_real(e, cls, tag, "kv", kv);
@@ -1125,6 +1137,20 @@ struct Compiler {
         bias[1] = -kp;
         // positive biasprm[2] on a position-like actuator means "dampratio" until set0 converts it
         bias[2] = has_dr && dampratio > 0 ? dampratio : -kv;
+        double timeconst = 0;
+        if (tag == "intvelocity") {
+          // an integrated-velocity servo: ctrl is the target's velocity, the activation the target
+          dyntype = MRS_DYN_INTEGRATOR;
+          if (actlimited == 0) fail(e, "intvelocity requires a limited activation");
+          if (!has_actrange) fail(e, "intvelocity requires actrange");
+          actlimited = 1;
+        } else if (get_real(e, cls, tag, "timeconst", timeconst)) {
+          if (timeconst < 0) fail(e, "timeconst must not be negative");
+          if (timeconst > 0) {
+            dyntype = MRS_DYN_FILTEREXACT;
+            dynprm[0] = timeconst;
+          }
+        }
       } else if (tag == "velocity") {
         double kv = 1;
         get_real(e, cls, tag, "kv", kv);
@@ -1144,7 +1170,20 @@ struct Compiler {
           else if (s == "affine") biastype = MRS_BIAS_AFFINE;
           else fail(e, "unsupported biastype " + s);
         }
-        if (get_str(e, cls, tag, "dyntype", s) && s != "none") fail(e, "actuator dynamics are not supported");
+        if (get_str(e, cls, tag, "dyntype", s)) {
+          if (s == "none") dyntype = MRS_DYN_NONE;
+          else if (s == "integrator") dyntype = MRS_DYN_INTEGRATOR;
+          else if (s == "filter") dyntype = MRS_DYN_FILTER;
+          else if (s == "filterexact") dyntype = MRS_DYN_FILTEREXACT;
+          else if (s == "muscle" || s == "user") fail(e, "dyntype " + s + " is not supported");
+          else fail(e, "unknown dyntype " + s);
+        }
+        get_reals(e, cls, tag, "dynprm", dynprm, 3);
+        int actdim = -1;
+        if (get_int(e, cls, tag, "actdim", actdim) && actdim >= 0) {
+          if (actdim > 1) fail(e, "actdim above 1 is not supported");
+          if (actdim != (dyntype == MRS_DYN_NONE ? 0 : 1)) fail(e, "actdim does not match the dyntype's own size");
+        }
         get_reals(e, cls, tag, "gainprm", gain, MRS_NGAIN);
         get_reals(e, cls, tag, "biasprm", bias, MRS_NBIAS);
       }
@@ -1157,7 +1196,14 @@ struct Compiler {
           (biastype == MRS_BIAS_AFFINE || gaintype == MRS_GAIN_AFFINE))
         fail(e, "velocity-dependent actuators on tendons are supported with the Euler and RK4 integrators only");
       m.actuator_trntype.push_back(trn);
-      m.actuator_dyntype.push_back(MRS_DYN_NONE);
+      m.actuator_dyntype.push_back(dyntype);
+      m.actuator_actadr.push_back(dyntype == MRS_DYN_NONE ? -1 : m.na);
+      m.actuator_actnum.push_back(dyntype == MRS_DYN_NONE ? 0 : 1);
+      m.actuator_actlimited.push_back(resolve(actlimited, has_actrange, actrange));
+      m.actuator_actearly.push_back(actearly);
+      m.actuator_dynprm.insert(m.actuator_dynprm.end(), dynprm, dynprm + 3);
+      m.actuator_actrange.insert(m.actuator_actrange.end(), actrange, actrange + 2);
+      if (dyntype != MRS_DYN_NONE) ++m.na;
       m.actuator_gaintype.push_back(gaintype);
       m.actuator_biastype.push_back(biastype);
       m.actuator_trnid.push_back(jid);
@@ -1268,7 +1314,7 @@ struct Compiler {
     for (auto& cp : sec->children) {
       const XmlElement* e = cp.get();
       if (e->tag != "key") fail(e, "unsupported keyframe element");
-      std::vector<double> qpos = m.qpos0, qvel(m.nv, 0.0), ctrl(m.nu, 0.0);
+      std::vector<double> qpos = m.qpos0, qvel(m.nv, 0.0), ctrl(m.nu, 0.0), act(m.na, 0.0);
       double time = 0;
       if (auto* s = e->attr("time")) time = parse_reals(*s, e, "time").at(0);
       auto fill = [&](const char* key, std::vector<double>& dst) {
@@ -1281,10 +1327,12 @@ struct Compiler {
       fill("qpos", qpos);
       fill("qvel", qvel);
       fill("ctrl", ctrl);
+      fill("act", act);
       m.key_time.push_back(time);
       m.key_qpos.insert(m.key_qpos.end(), qpos.begin(), qpos.end());
       m.key_qvel.insert(m.key_qvel.end(), qvel.begin(), qvel.end());
       m.key_ctrl.insert(m.key_ctrl.end(), ctrl.begin(), ctrl.end());
+      m.key_act.insert(m.key_act.end(), act.begin(), act.end());
       ++m.nkey;
     }
   }
@@ -2349,6 +2397,8 @@ mrs_model_view Model::view() const {
   MRS_V(mesh_polyadr); MRS_V(mesh_polynum); MRS_V(mesh_polyvertadr); MRS_V(mesh_polyvert); MRS_V(mesh_polynormal);
   v.mesh_polyvertnum = mesh_polynum_v.empty() ? nullptr : mesh_polynum_v.data();
   MRS_V(site_type); MRS_V(site_size);
+  MRS_V(actuator_actadr); MRS_V(actuator_actnum); MRS_V(actuator_actlimited); MRS_V(actuator_actearly);
+  MRS_V(actuator_dynprm); MRS_V(actuator_actrange); MRS_V(key_act);
 #undef MRS_V
   return v;
 }

@@ -50,6 +50,9 @@ struct Model {
       actuator_trnid, actuator_ctrllimited, actuator_forcelimited;
   std::vector<double> actuator_gear, actuator_gainprm, actuator_biasprm, actuator_ctrlrange,
       actuator_forcerange;
+  // activation state (mrs_model_view actuator_act* / actuator_dynprm): na stateful actuators
+  std::vector<int> actuator_actadr, actuator_actnum, actuator_actlimited, actuator_actearly;
+  std::vector<double> actuator_dynprm, actuator_actrange, key_act;
 
   std::vector<int> sensor_type, sensor_objtype, sensor_objid, sensor_dim, sensor_adr;
   std::vector<double> sensor_cutoff;

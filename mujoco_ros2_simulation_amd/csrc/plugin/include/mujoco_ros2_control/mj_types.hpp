@@ -7,7 +7,7 @@
 // are mjModel's: m->nq, m->jnt_qposadr[j], m->sensor_adr[s], ...) plus mjOption under m->opt; it
 // owns a private copy of the compiled model, so a copy outlives the plugin exactly as
 // mj_copyModel's does.  mjData holds the host mirror of one environment's state arrays under
-// mjData's names, in one allocation (xfrc_applied, appended after the first members, lies in it too).  The five lifecycle functions keep MuJoCo's names and
+// mjData's names, in one allocation (xfrc_applied and act, appended after the first members, lie in it too).  The five lifecycle functions keep MuJoCo's names and
 // argument conventions (dest == nullptr allocates); they are this library's own.
 #pragma once
 
@@ -42,6 +42,8 @@ struct mjData_ {
   double* buffer;               // the one allocation behind the arrays
   double* xfrc_applied;         // 6 * nbody: per body a world-frame force, then torque, at its centre of mass
   int nbody;
+  double* act;                  // na: activations of the stateful actuators (m->actuator_actadr[i], -1 none)
+  int na;
 };
 typedef struct mjData_ mjData;
 

@@ -59,7 +59,9 @@ mjData* mj_makeData(const mjModel* m) {
   d->nu = m->nu;
   d->nsensordata = m->nsensordata;
   d->nbody = m->nbody;
-  const size_t n = size_t(d->nq) + 5 * size_t(d->nv) + size_t(d->nu) + size_t(d->nsensordata) + 6 * size_t(d->nbody);
+  d->na = m->na;
+  const size_t n = size_t(d->nq) + 5 * size_t(d->nv) + size_t(d->nu) + size_t(d->nsensordata) + 6 * size_t(d->nbody) +
+                   size_t(d->na);
   d->buffer = new double[n > 0 ? n : 1]();
   double* p = d->buffer;
   auto take = [&p](int k) { double* r = p; p += k; return r; };
@@ -72,19 +74,21 @@ mjData* mj_makeData(const mjModel* m) {
   d->qfrc_actuator = take(d->nv);
   d->sensordata = take(d->nsensordata);
   d->xfrc_applied = take(6 * d->nbody);
+  d->act = take(d->na);
   return d;
 }
 
 mjData* mj_copyData(mjData* dest, const mjModel* m, const mjData* src) {
   if (!m || !src) return nullptr;
   if (src->nq != m->nq || src->nv != m->nv || src->nu != m->nu || src->nsensordata != m->nsensordata ||
-      src->nbody != m->nbody)
+      src->nbody != m->nbody || src->na != m->na)
     return nullptr;
   if (!dest) dest = mj_makeData(m);
   else if (dest->nq != m->nq || dest->nv != m->nv || dest->nu != m->nu || dest->nsensordata != m->nsensordata ||
-           dest->nbody != m->nbody)
+           dest->nbody != m->nbody || dest->na != m->na)
     return nullptr;
-  const size_t n = size_t(m->nq) + 5 * size_t(m->nv) + size_t(m->nu) + size_t(m->nsensordata) + 6 * size_t(m->nbody);
+  const size_t n = size_t(m->nq) + 5 * size_t(m->nv) + size_t(m->nu) + size_t(m->nsensordata) + 6 * size_t(m->nbody) +
+                   size_t(m->na);
   if (dest != src) std::memcpy(dest->buffer, src->buffer, n * sizeof(double));
   dest->time = src->time;
   return dest;

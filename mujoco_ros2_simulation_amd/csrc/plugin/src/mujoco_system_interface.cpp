@@ -621,6 +621,7 @@ void MujocoSystemInterface::pull_state_locked() {
     mrs_batch_get_field(batch_, MRS_FIELD_QACC, mj_data_->qacc, 0, 1);
     mrs_batch_get_field(batch_, MRS_FIELD_QACC_WARMSTART, mj_data_->qacc_warmstart, 0, 1);
   }
+  if (view_.na > 0) mrs_batch_get_act(batch_, mj_data_->act, 0, 1);
   mrs_batch_get_field(batch_, MRS_FIELD_TIME, &mj_data_->time, 0, 1);
   // sim -> control copy of the outputs (mj_copyData(control <- sim), reference :1759); the control
   // inputs ctrl / qfrc_applied stay what write() put there
@@ -633,6 +634,7 @@ void MujocoSystemInterface::pull_state_locked() {
   std::copy(d.qfrc_actuator, d.qfrc_actuator + d.nv, c.qfrc_actuator);
   std::copy(d.sensordata, d.sensordata + d.nsensordata, c.sensordata);
   std::copy(d.xfrc_applied, d.xfrc_applied + 6 * d.nbody, c.xfrc_applied);
+  std::copy(d.act, d.act + d.na, c.act);
   c.time = d.time;
 }
 
@@ -761,6 +763,7 @@ void MujocoSystemInterface::set_data(mjData* mj_data) {
   }
   push_xfrc_locked();
   if (view_.nu > 0) mrs_batch_set_field(batch_, MRS_FIELD_CTRL, mj_data_->ctrl, 0, 1);
+  if (view_.na > 0) mrs_batch_set_act(batch_, mj_data_->act, 0, 1);
   mrs_batch_set_field(batch_, MRS_FIELD_TIME, &mj_data_->time, 0, 1);
   mrs_batch_forward(batch_);
   mrs_batch_sync(batch_);

@@ -151,6 +151,13 @@ _POLY_ARRAYS = [
 ]
 # site shapes (after the polygon block)
 _SITE_ARRAYS = [("site_type", "i", "nsite", 1), ("site_size", "d", "nsite", 3)]
+# activation state (after the site shapes): na stateful actuators, one activation each
+_ACT_ARRAYS = [
+    ("actuator_actadr", "i", "nu", 1), ("actuator_actnum", "i", "nu", 1), ("actuator_actlimited", "i", "nu", 1),
+    ("actuator_actearly", "i", "nu", 1), ("actuator_dynprm", "d", "nu", 3), ("actuator_actrange", "d", "nu", 2),
+    ("key_act", "d", "nkey", "na"),
+]
+DYN_NONE, DYN_INTEGRATOR, DYN_FILTER, DYN_FILTEREXACT = range(4)
 
 
 class ModelView(C.Structure):
@@ -174,7 +181,8 @@ class ModelView(C.Structure):
                 [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _TEN_ARRAYS] +
                 [(n, C.c_int) for n in _POLY_SIZES] +
                 [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _POLY_ARRAYS] +
-                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _SITE_ARRAYS])
+                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _SITE_ARRAYS] +
+                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _ACT_ARRAYS])
 
 
 _lib = None
@@ -215,6 +223,10 @@ def lib() -> C.CDLL:
         L.mrs_batch_get_field.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.mrs_batch_device_ptr.restype = C.c_void_p
         L.mrs_batch_device_ptr.argtypes = [C.c_void_p, C.c_int]
+        L.mrs_batch_set_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.mrs_batch_get_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.mrs_batch_act_device_ptr.restype = C.c_void_p
+        L.mrs_batch_act_device_ptr.argtypes = [C.c_void_p]
         L.mrs_batch_set_ctrl_device.argtypes = [C.c_void_p, C.c_void_p]
         L.mrs_batch_bind_ctrl_device.argtypes = [C.c_void_p, C.c_void_p]
         L.mrs_batch_set_timing.argtypes = [C.c_void_p, C.c_int]
@@ -278,7 +290,7 @@ class Model:
         self.gravity = np.array(v.gravity[:])
         self.vis_headlight = np.array(v.vis_headlight[:])
         for name, kind, count, width in (_ARRAYS + _MESH_ARRAYS + _CONTACT_ARRAYS + _EQ_ARRAYS + _REND_ARRAYS +
-                                         _TEN_ARRAYS + _POLY_ARRAYS + _SITE_ARRAYS):
+                                         _TEN_ARRAYS + _POLY_ARRAYS + _SITE_ARRAYS + _ACT_ARRAYS):
             n = getattr(v, count)
             w = getattr(v, width) if isinstance(width, str) else width
             ptr = getattr(v, name)
@@ -379,6 +391,23 @@ class Batch:
             return
         a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self._dim(field))
         _check(lib().mrs_batch_set_field(self._h, field, a.ctypes.data, env0, a.shape[0]))
+
+    def get_act(self, env0: int = 0, n: int | None = None) -> np.ndarray:
+        """mjData.act [n, na]: the activations of the stateful actuators, by actuator_actadr"""
+        n = self.n - env0 if n is None else n
+        out = np.empty((n, self.model.na), dtype=np.float64)
+        _check(lib().mrs_batch_get_act(self._h, out.ctypes.data, env0, n))
+        return out
+
+    def set_act(self, values, env0: int = 0) -> None:
+        if self.model.na == 0:
+            return
+        a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.model.na)
+        _check(lib().mrs_batch_set_act(self._h, a.ctypes.data, env0, a.shape[0]))
+
+    def act_device_ptr(self) -> int:
+        """the activations on the device, fp32 [n, na], ordered on the batch stream (0 when na == 0)"""
+        return lib().mrs_batch_act_device_ptr(self._h) or 0
 
     def reset(self, key: int = -1, env0: int = 0, n: int | None = None) -> None:
         _check(lib().mrs_batch_reset(self._h, key, env0, self.n - env0 if n is None else n))
