@@ -173,6 +173,20 @@ int mrs_batch_get_act(mrs_batch* b, double* host, int env0, int n);
 /* device pointer of the activations, [n_envs][na] fp32; accesses ordered on the batch stream see the
  * launches' values.  NULL when na == 0. */
 float* mrs_batch_act_device_ptr(mrs_batch* b);
+/* mjData.mocap_pos / mocap_quat: the world poses of the model's nmocap mocap bodies (mrs_model_view
+ * body_mocapid gives each one's row).  Input state like ctrl: a launch reads them at its start and
+ * holds them over its n steps (and RK4's stages); the buffer keeps what the caller wrote and the
+ * kinematics normalise the quaternion they read.  They start at the bodies' pos / quat; every reset
+ * writes the reset envs' rows (a keyframe's mpos / mquat, else the bodies' pos / quat), the NaN
+ * auto-reset too.  Not MRS_FIELD_* values: host layout pos [n][nmocap][3], quat [n][nmocap][4] fp64 for
+ * envs [env0, env0+n); either pointer may be NULL (that part is left as it is / not read back); with
+ * nmocap == 0 set / get succeed and copy nothing. */
+int mrs_batch_set_mocap(mrs_batch* b, const double* pos, const double* quat, int env0, int n);
+int mrs_batch_get_mocap(mrs_batch* b, double* pos, double* quat, int env0, int n);
+/* device pointers of the poses, [n_envs][nmocap][3] and [n_envs][nmocap][4] fp32; a write ordered on the
+ * batch stream takes effect at the next step / forward launch.  NULL when nmocap == 0. */
+float* mrs_batch_mocap_pos_device_ptr(mrs_batch* b);
+float* mrs_batch_mocap_quat_device_ptr(mrs_batch* b);
 
 /* replaces mj_step (src/mujoco_system_interface.cpp:1691,1731): advance every env n_steps times,
  * fused in one launch; ctrl / qfrc_applied are held constant (zero-order hold) across the n steps,

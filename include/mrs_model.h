@@ -212,6 +212,15 @@ typedef struct mrs_model_view {
    * every advance; actearly: the force uses the next activation.  key_act [nkey][na]. */
   const int *actuator_actadr, *actuator_actnum, *actuator_actlimited, *actuator_actearly;
   const double *actuator_dynprm /*3*/, *actuator_actrange /*2*/, *key_act;
+
+  /* mocap bodies (mjModel nmocap / body_mocapid, mjData.mocap_pos / mocap_quat): children of the world
+   * without joints whose world pose is per-env input state, not a model constant.  body_mocapid[nbody]
+   * is the body's row in mocap_pos [nmocap][3] / mocap_quat [nmocap][4] (-1: not a mocap body; ids in
+   * body order).  body_pos / body_quat hold the start pose; body_weldid stays 0.  key_mpos
+   * [nkey][3 nmocap], key_mquat [nkey][4 nmocap] (a key without the attribute: the start pose). */
+  int nmocap;
+  const int *body_mocapid;
+  const double *key_mpos, *key_mquat;
 } mrs_model_view;
 
 #ifdef __cplusplus

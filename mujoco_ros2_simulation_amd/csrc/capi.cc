@@ -277,6 +277,23 @@ int mrs_batch_get_act(mrs_batch* b, double* host, int env0, int n) {
 
 float* mrs_batch_act_device_ptr(mrs_batch* b) { return b ? mrs::batch_act_device_ptr(b->impl) : nullptr; }
 
+int mrs_batch_set_mocap(mrs_batch* b, const double* pos, const double* quat, int env0, int n) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_set_mocap(b->impl, pos, quat, env0, n);
+  });
+}
+
+int mrs_batch_get_mocap(mrs_batch* b, double* pos, double* quat, int env0, int n) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_get_mocap(b->impl, pos, quat, env0, n);
+  });
+}
+
+float* mrs_batch_mocap_pos_device_ptr(mrs_batch* b) { return b ? mrs::batch_mocap_pos_device_ptr(b->impl) : nullptr; }
+float* mrs_batch_mocap_quat_device_ptr(mrs_batch* b) { return b ? mrs::batch_mocap_quat_device_ptr(b->impl) : nullptr; }
+
 int mrs_batch_step(mrs_batch* b, int n_steps) {
   return guarded([&] {
     if (!b) throw std::invalid_argument("null batch");

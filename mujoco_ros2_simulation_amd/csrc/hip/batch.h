@@ -31,6 +31,11 @@ void* batch_device_ptr(BatchImpl* b, int field);
 void batch_set_act(BatchImpl* b, const double* host, int env0, int n);
 void batch_get_act(BatchImpl* b, double* host, int env0, int n);
 float* batch_act_device_ptr(BatchImpl* b);  // null when na == 0
+// the mocap poses [n][nmocap][3] / [n][nmocap][4] (mjData.mocap_pos / mocap_quat); a null part is skipped
+void batch_set_mocap(BatchImpl* b, const double* pos, const double* quat, int env0, int n);
+void batch_get_mocap(BatchImpl* b, double* pos, double* quat, int env0, int n);
+float* batch_mocap_pos_device_ptr(BatchImpl* b);   // null when nmocap == 0
+float* batch_mocap_quat_device_ptr(BatchImpl* b);  // null when nmocap == 0
 void batch_set_ctrl_device(BatchImpl* b, const float* d_ctrl);
 void batch_bind_ctrl_device(BatchImpl* b, const float* d_ctrl);  // zero-copy ctrl source (null: own buffer)
 void batch_set_timing(BatchImpl* b, int mask);  // launches timed for batch_last_kernel_ms (bit 0 step, 1 frames)

@@ -881,12 +881,14 @@ __global__ __launch_bounds__(256) void depth_kernel_mesh(const int* geom_type, c
 struct ResetArgs {
   const unsigned char* mask;  // [n]
   const int* keys;            // [n] start indices, or null: `key` for every env
-  int key, n, nq, nv, nu, na, nx, nkey, npool;
+  int key, n, nq, nv, nu, na, nx, nkey, npool, nmocap;
   const float *tab_qpos, *tab_qvel, *tab_ctrl, *tab_act;  // [1 + nkey][nq | nv | nu | na]
+  const float *tab_mpos, *tab_mquat;                      // [1 + nkey][3 nmocap | 4 nmocap]
   const double* tab_time;                       // [1 + nkey]
   const float *pool_qpos, *pool_qvel;           // [npool][nq | nv]
   float *qpos, *qvel, *ctrl, *qfrc_applied, *qacc_ws, *xfrc;  // ctrl / xfrc null: not written
   float* act;  // [n][na] (null when na == 0)
+  float *mocap_pos, *mocap_quat;  // [n][nmocap][3 | 4] (null when nmocap == 0)
   double* time;
   int* warning;
 };
@@ -921,6 +923,11 @@ __global__ __launch_bounds__(256) void reset_masked_kernel(const ResetArgs a) {
   if (a.xfrc)
     for (int i = lane; i < a.nx; i += 16) a.xfrc[e * a.nx + i] = 0;
   for (int i = lane; i < a.na; i += 16) a.act[e * a.na + i] = sa ? sa[i] : 0.0f;
+  {  // mocap poses: the keyframe's, else (qpos0 and pool rows) the bodies' pos / quat in row 0
+    const size_t row = k < a.nkey ? static_cast<size_t>(k + 1) : 0;
+    for (int i = lane; i < 3 * a.nmocap; i += 16) a.mocap_pos[e * 3 * a.nmocap + i] = a.tab_mpos[row * 3 * a.nmocap + i];
+    for (int i = lane; i < 4 * a.nmocap; i += 16) a.mocap_quat[e * 4 * a.nmocap + i] = a.tab_mquat[row * 4 * a.nmocap + i];
+  }
   if (lane < 4) a.warning[e * 4 + lane] = 0;
   if (lane == 4) a.time[e] = t;
 }
@@ -970,6 +977,7 @@ struct BatchImpl {
   // model's table [1 + nkey] (row 0 qpos0 with zero qvel / ctrl / time, row 1 + k keyframe k; made at
   // batch creation) and the runtime pool [pool_n] of batch_set_start_states (capacity pool_cap rows)
   float *tab_qpos = nullptr, *tab_qvel = nullptr, *tab_ctrl = nullptr, *tab_act = nullptr;
+  float *tab_mpos = nullptr, *tab_mquat = nullptr;  // the mocap poses' rows (row 0: the bodies' pos / quat)
   double* tab_time = nullptr;
   float *pool_qpos = nullptr, *pool_qvel = nullptr;
   int pool_n = 0, pool_cap = 0;
@@ -1148,6 +1156,12 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
     if (t == MRS_SENS_TOUCH) d.acc_sens |= 2;        // reads the row forces
   }
   d.na = m.na;
+  d.nmocap = m.nmocap;
+  // a body whose world pose is the same in every env for good: welded to the world and not on or
+  // below a mocap body (whose pose is per-env state)
+  auto fixed_in_world = [&](int body) {
+    return m.body_weldid[body] == 0 && m.body_mocapid[m.body_rootid[body]] < 0;
+  };
   d.nq = m.nq; d.nv = m.nv; d.nu = m.nu; d.nbody = m.nbody; d.njnt = m.njnt; d.ngeom = m.ngeom;
   d.nsite = m.nsite; d.ncam = m.ncam; d.nsensor = m.nsensor; d.nsensordata = m.nsensordata;
   d.max_depth = m.max_depth;
@@ -1680,6 +1694,7 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
       for (int i = 0; i < 3; ++i) kb.push_back(static_cast<float>(m.body_inertia[3 * b + i]));
       kb.push_back(fbits(m.body_jntadr[b]));
       kb.push_back(fbits(m.body_jntnum[b]));
+      kb.push_back(fbits(m.body_mocapid[b] + 1));  // (0: not a mocap body, as the pad was)
       while (kb.size() % 25) kb.push_back(0.0f);
     }
     for (int j = 0; j < m.njnt; ++j) {
@@ -1880,7 +1895,7 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
   d.rf_static_frame = 0;
   if (d.nrf > 0) {
     bool all_static = true;
-    for (int k = 0; k < d.nrf; ++k) all_static = all_static && m.body_weldid[m.site_bodyid[m.sensor_objid[rf[k]]]] == 0;
+    for (int k = 0; k < d.nrf; ++k) all_static = all_static && fixed_in_world(m.site_bodyid[m.sensor_objid[rf[k]]]);
     d.rf_static_frame = all_static && !std::getenv("MRS_NO_STATIC_FRAME") ? 1 : 0;
   }
   auto body_world = [&](int b, double R[9], double p[3]) {  // world pose of a body without joints above it
@@ -1996,6 +2011,7 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
     L.Li = blocked && m.solver == MRS_SOL_PGS ? take(std::max(1, d.nMblk)) : 0;
     L.rk = m.integrator == MRS_INT_RK4 ? take(std::max(1, m.nq) + 4 * nv) : 0;
     L.act = m.na > 0 ? take(4 * m.na) : 0;
+    L.mocap = m.nmocap > 0 ? take(7 * m.nmocap) : 0;
     L.total = off;
   };
   lds_layout(false);
@@ -2005,10 +2021,10 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
   if (d.nrfblk > 0 && d.nrgeom <= 32) {
     bool static_rays = true;
     for (int k = 0; k < d.nrf; ++k)
-      if (m.body_weldid[m.site_bodyid[m.sensor_objid[rf[k]]]] != 0) static_rays = false;
+      if (!fixed_in_world(m.site_bodyid[m.sensor_objid[rf[k]]])) static_rays = false;
     for (int i = 0, g = 0; g < m.ngeom; ++g) {
       if (m.geom_rgba[4 * g + 3] == 0) continue;
-      if (m.body_weldid[m.geom_bodyid[g]] == 0) d.rf_static_mask |= 1u << i;
+      if (fixed_in_world(m.geom_bodyid[g])) d.rf_static_mask |= 1u << i;
       ++i;
     }
     if (static_rays && d.rf_static_mask && !std::getenv("MRS_NO_STATIC_RAYS")) d.rf_mode = 2;
@@ -2266,6 +2282,9 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
   S.sens = take(std::max(1, m.nsensordata));
   S.xfrc = take(1);
   S.total = off;
+  // the mocap poses (batch_reset fills them)
+  d.mocap_pos = m.nmocap > 0 ? static_cast<float*>(dalloc(b, static_cast<size_t>(b.n) * 3 * m.nmocap * sizeof(float))) : nullptr;
+  d.mocap_quat = m.nmocap > 0 ? static_cast<float*>(dalloc(b, static_cast<size_t>(b.n) * 4 * m.nmocap * sizeof(float))) : nullptr;
   b.d_dm = static_cast<DevModel*>(dalloc(b, sizeof(DevModel)));
   HIP_CHECK(hipMemcpyAsync(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice, b.stream));
   HIP_CHECK(hipStreamSynchronize(b.stream));
@@ -2325,20 +2344,31 @@ void upload_start_table(BatchImpl& b) {
   const Model& m = *b.model;
   const size_t rows = static_cast<size_t>(m.nkey) + 1;
   std::vector<float> q(rows * m.nq), v(rows * m.nv, 0.0f), c(rows * m.nu, 0.0f), a(rows * m.na, 0.0f);
+  std::vector<float> mp(rows * 3 * m.nmocap), mq(rows * 4 * m.nmocap);
   std::vector<double> t(rows, 0.0);
   for (int i = 0; i < m.nq; ++i) q[i] = static_cast<float>(m.qpos0[i]);
+  for (int bd = 0; bd < m.nbody; ++bd) {
+    const int id = m.body_mocapid[bd];
+    if (id < 0) continue;
+    for (int i = 0; i < 3; ++i) mp[3 * id + i] = static_cast<float>(m.body_pos[3 * bd + i]);
+    for (int i = 0; i < 4; ++i) mq[4 * id + i] = static_cast<float>(m.body_quat[4 * bd + i]);
+  }
   for (int k = 0; k < m.nkey; ++k) {
     const size_t r = static_cast<size_t>(k) + 1, s = static_cast<size_t>(k);
     for (int i = 0; i < m.nq; ++i) q[r * m.nq + i] = static_cast<float>(m.key_qpos[s * m.nq + i]);
     for (int i = 0; i < m.nv; ++i) v[r * m.nv + i] = static_cast<float>(m.key_qvel[s * m.nv + i]);
     for (int i = 0; i < m.nu; ++i) c[r * m.nu + i] = static_cast<float>(m.key_ctrl[s * m.nu + i]);
     for (int i = 0; i < m.na; ++i) a[r * m.na + i] = static_cast<float>(m.key_act[s * m.na + i]);
+    for (int i = 0; i < 3 * m.nmocap; ++i) mp[r * 3 * m.nmocap + i] = static_cast<float>(m.key_mpos[s * 3 * m.nmocap + i]);
+    for (int i = 0; i < 4 * m.nmocap; ++i) mq[r * 4 * m.nmocap + i] = static_cast<float>(m.key_mquat[s * 4 * m.nmocap + i]);
     t[r] = m.key_time[k];
   }
   b.tab_qpos = static_cast<float*>(dalloc(b, q.size() * sizeof(float)));
   b.tab_qvel = static_cast<float*>(dalloc(b, v.size() * sizeof(float)));
   b.tab_ctrl = static_cast<float*>(dalloc(b, c.size() * sizeof(float)));
   b.tab_act = static_cast<float*>(dalloc(b, a.size() * sizeof(float)));
+  b.tab_mpos = static_cast<float*>(dalloc(b, mp.size() * sizeof(float)));
+  b.tab_mquat = static_cast<float*>(dalloc(b, mq.size() * sizeof(float)));
   b.tab_time = static_cast<double*>(dalloc(b, t.size() * sizeof(double)));
   auto put = [&](void* dst, const void* src, size_t bytes) {
     if (bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, b.stream));
@@ -2347,6 +2377,8 @@ void upload_start_table(BatchImpl& b) {
   put(b.tab_qvel, v.data(), v.size() * sizeof(float));
   put(b.tab_ctrl, c.data(), c.size() * sizeof(float));
   put(b.tab_act, a.data(), a.size() * sizeof(float));
+  put(b.tab_mpos, mp.data(), mp.size() * sizeof(float));
+  put(b.tab_mquat, mq.data(), mq.size() * sizeof(float));
   put(b.tab_time, t.data(), t.size() * sizeof(double));
   HIP_CHECK(hipStreamSynchronize(b.stream));
 }
@@ -2519,6 +2551,19 @@ void batch_reset(BatchImpl* b, int key, int env0, int n) {
                   &act[static_cast<size_t>(e) * m.na]);
     batch_set_act(b, act.data(), env0, n);
   }
+  if (m.nmocap > 0) {  // (mj_resetData: the bodies' pos / quat; mj_resetDataKeyframe: key_mpos / key_mquat)
+    std::vector<double> mp(static_cast<size_t>(n) * 3 * m.nmocap), mq(static_cast<size_t>(n) * 4 * m.nmocap);
+    for (int e = 0; e < n; ++e)
+      for (int bd = 0; bd < m.nbody; ++bd) {
+        const int id = m.body_mocapid[bd];
+        if (id < 0) continue;
+        const double* p = key >= 0 ? &m.key_mpos[(static_cast<size_t>(key) * m.nmocap + id) * 3] : &m.body_pos[3 * bd];
+        const double* q = key >= 0 ? &m.key_mquat[(static_cast<size_t>(key) * m.nmocap + id) * 4] : &m.body_quat[4 * bd];
+        std::copy(p, p + 3, &mp[(static_cast<size_t>(e) * m.nmocap + id) * 3]);
+        std::copy(q, q + 4, &mq[(static_cast<size_t>(e) * m.nmocap + id) * 4]);
+      }
+    batch_set_mocap(b, mp.data(), mq.data(), env0, n);
+  }
   std::vector<double> w(static_cast<size_t>(n) * 4, 0.0);
   batch_set(b, MRS_FIELD_WARNING, w.data(), env0, n);
   if (b->st.xfrc_applied) {  // (mj_resetData zeroes xfrc_applied)
@@ -2570,7 +2615,8 @@ void batch_reset_masked_device(BatchImpl* b, const unsigned char* d_mask, const 
   a.mask = d_mask;
   a.keys = d_key;
   a.key = key < 0 ? -1 : key;
-  a.n = b->n; a.nq = m.nq; a.nv = m.nv; a.nu = m.nu; a.na = m.na; a.nx = 6 * m.nbody;
+  a.n = b->n; a.nq = m.nq; a.nv = m.nv; a.nu = m.nu; a.na = m.na; a.nx = 6 * m.nbody; a.nmocap = m.nmocap;
+  a.tab_mpos = b->tab_mpos; a.tab_mquat = b->tab_mquat; a.mocap_pos = b->dm.mocap_pos; a.mocap_quat = b->dm.mocap_quat;
   a.nkey = m.nkey; a.npool = b->pool_n;
   a.tab_qpos = b->tab_qpos; a.tab_qvel = b->tab_qvel; a.tab_ctrl = b->tab_ctrl; a.tab_act = b->tab_act; a.tab_time = b->tab_time;
   a.pool_qpos = b->pool_qpos; a.pool_qvel = b->pool_qvel;
@@ -2691,6 +2737,45 @@ void batch_get_act(BatchImpl* b, double* host, int env0, int n) {
 }
 
 float* batch_act_device_ptr(BatchImpl* b) { return b->st.act; }
+
+void batch_set_mocap(BatchImpl* b, const double* pos, const double* quat, int env0, int n) {
+  const int nm = b->model->nmocap;
+  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
+  if (n == 0 || nm == 0 || (!pos && !quat)) return;
+  HIP_CHECK(hipSetDevice(b->device));
+  std::vector<float> tp, tq;
+  auto put = [&](float* dst, const double* src, int w, std::vector<float>& tmp) {
+    if (!src) return;
+    const size_t cnt = static_cast<size_t>(n) * nm * w;
+    tmp.resize(cnt);
+    for (size_t i = 0; i < cnt; ++i) tmp[i] = static_cast<float>(src[i]);
+    HIP_CHECK(hipMemcpyAsync(dst + static_cast<size_t>(env0) * nm * w, tmp.data(), cnt * sizeof(float),
+                             hipMemcpyHostToDevice, b->stream));
+  };
+  put(b->dm.mocap_pos, pos, 3, tp);
+  put(b->dm.mocap_quat, quat, 4, tq);
+  HIP_CHECK(hipStreamSynchronize(b->stream));
+}
+
+void batch_get_mocap(BatchImpl* b, double* pos, double* quat, int env0, int n) {
+  const int nm = b->model->nmocap;
+  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
+  if (n == 0 || nm == 0 || (!pos && !quat)) return;
+  HIP_CHECK(hipSetDevice(b->device));
+  std::vector<float> tp(pos ? static_cast<size_t>(n) * nm * 3 : 0), tq(quat ? static_cast<size_t>(n) * nm * 4 : 0);
+  if (pos)
+    HIP_CHECK(hipMemcpyAsync(tp.data(), b->dm.mocap_pos + static_cast<size_t>(env0) * nm * 3, tp.size() * sizeof(float),
+                             hipMemcpyDeviceToHost, b->stream));
+  if (quat)
+    HIP_CHECK(hipMemcpyAsync(tq.data(), b->dm.mocap_quat + static_cast<size_t>(env0) * nm * 4, tq.size() * sizeof(float),
+                             hipMemcpyDeviceToHost, b->stream));
+  HIP_CHECK(hipStreamSynchronize(b->stream));
+  for (size_t i = 0; i < tp.size(); ++i) pos[i] = tp[i];
+  for (size_t i = 0; i < tq.size(); ++i) quat[i] = tq[i];
+}
+
+float* batch_mocap_pos_device_ptr(BatchImpl* b) { return b->dm.mocap_pos; }
+float* batch_mocap_quat_device_ptr(BatchImpl* b) { return b->dm.mocap_quat; }
 
 void batch_bind_ctrl_device(BatchImpl* b, const float* d_ctrl) { b->ctrl_bound = d_ctrl; }
 

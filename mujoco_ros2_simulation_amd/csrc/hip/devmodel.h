@@ -50,8 +50,10 @@ struct LdsLayout {
       niter,   // constraint solver iterations of the last forward (int bits)
       hcon,    // helper waves: the step's contact and row counts from the helper (int bits)
       Lh,      // helper waves: the factor of M + h D for the integrator, built by the helper (0: none)
-      act;     // models with stateful actuators (na > 0): act [na], act_dot [na], and RK4's initial act and
+      act,     // models with stateful actuators (na > 0): act [na], act_dot [na], and RK4's initial act and
                // B-weighted sum of the stages' act_dot [na each]
+      mocap;   // models with mocap bodies (nmocap > 0): per mocap body pos[3], then the quaternion as the
+               // caller wrote it [4] (7 floats each), loaded at launch start and held like ctrl
   int total;  // floats per env (multiple of 4)
 };
 
@@ -234,6 +236,13 @@ struct DevModel {
   // dynamics records (batch.hip actdyn, 8 floats each; packed only when na > 0)
   int na;
   CPtr<float> actdyn;
+  // mocap bodies (mjData.mocap_pos / mocap_quat): their count -- 0 for every model
+  // without one, whose launches then take none of the mocap code -- and the batch's per-env poses, input
+  // state like ctrl: [n_envs][nmocap][3] and [n_envs][nmocap][4], the quaternion as the caller wrote it
+  // (body_pose normalises what it reads).  A body's row is kinbody[19] - 1 (0: not a mocap body).  Kept
+  // here, not in DevState, so the kernels' arguments are what they were
+  int nmocap;
+  float *mocap_pos, *mocap_quat;
 };
 constexpr int kRayBlock = 128;
 

@@ -2064,6 +2064,19 @@ __device__ __forceinline__ void body_pose(const DevModel& m, lfloat* s, int b, c
   const LdsLayout& L = m.L;
   const auto kb = kin_body<G>(m, b);
   const int ja = __float_as_int(kb[17]), nj = __float_as_int(kb[18]);
+  // a mocap body (a jointless child of the world): its world pose is the env's mocap_pos and the
+  // normalised mocap_quat (mj_kinematics), from the launch's LDS copy -- all three kinematics paths
+  // take a body's local pose here
+  if (m.nmocap > 0) {
+    const int mid = __float_as_int(kb[19]);
+    if (mid > 0) {
+      const lfloat* mc = s + L.mocap + 7 * (mid - 1);
+      pos[0] = mc[0]; pos[1] = mc[1]; pos[2] = mc[2];
+      q[0] = mc[3]; q[1] = mc[4]; q[2] = mc[5]; q[3] = mc[6];
+      quat_normalize(q);
+      return;
+    }
+  }
   if (nj > 0 && __float_as_int(kin_jnt<G>(m, ja)[7]) == MRS_JNT_FREE) {
     const lfloat* qp = s + L.qpos + __float_as_int(kin_jnt<G>(m, ja)[6]);
     pos[0] = qp[0]; pos[1] = qp[1]; pos[2] = qp[2];
@@ -7423,6 +7436,16 @@ __device__ MRS_PHASE void reset_env(ENV_PARAMS) {
   for (int i = lane; i < m.nv; i += G) { s[L.qvel + i] = 0; s[L.qacc_ws + i] = 0; }
   #pragma unroll 1
   for (int i = lane; i < m.na; i += G) s[L.act + i] = 0;
+  // (mj_resetData: mocap_pos / mocap_quat back to the bodies' pos / quat; the launch stores them)
+  if (m.nmocap > 0) {
+    #pragma unroll 1
+    for (int b = lane; b < m.nbody; b += G) {
+      const auto kb = kin_body<G>(m, b);
+      const int mid = __float_as_int(kb[19]);
+      if (mid > 0)
+        for (int i = 0; i < 7; ++i) s[L.mocap + 7 * (mid - 1) + i] = kb[i];
+    }
+  }
   wsync();
 }
 
@@ -7908,6 +7931,14 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
     s[L.act + i] = st.act[e * m.na + i];
     s[L.act + m.na + i] = 0;
   }
+  // the env's mocap poses, held over the launch's steps (and RK4's stages) like ctrl
+  if (m.nmocap > 0) {
+    #pragma unroll 1
+    for (int i = lane; i < (is_helper ? 0 : 7 * m.nmocap); i += G) {
+      const int k = i / 7, c = i - 7 * k;
+      s[L.mocap + i] = c < 3 ? m.mocap_pos[(e * m.nmocap + k) * 3 + c] : m.mocap_quat[(e * m.nmocap + k) * 4 + c - 3];
+    }
+  }
   // xfrc_applied in use: the group's row of it for the phases (xfrc_row) -- a mirror group reads its
   // primary's env, a group past n_envs none
   if (st.xfrc_applied && lane == 0 && !is_helper) scr[m.S.xfrc] = __int_as_float(env < n_envs ? env : -1);
@@ -8103,6 +8134,16 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
   }
   #pragma unroll 1
   for (int i = lane; i < m.na; i += G) st.act[e * m.na + i] = s[L.act + i];
+  // an auto-reset put the env's mocap poses back to the bodies' pos / quat: store them (no other
+  // launch writes the buffers, which are the caller's input)
+  if (m.nmocap > 0 && (w_pos | w_vel | w_acc) && !(m.disableflags & MRS_DSBL_AUTORESET)) {
+    #pragma unroll 1
+    for (int i = lane; i < 7 * m.nmocap; i += G) {
+      const int k = i / 7, c = i - 7 * k;
+      if (c < 3) m.mocap_pos[(e * m.nmocap + k) * 3 + c] = s[L.mocap + i];
+      else m.mocap_quat[(e * m.nmocap + k) * 4 + c - 3] = s[L.mocap + i];
+    }
+  }
   if (lane == 0) {
     st.time[e] = time;
     st.ncon[e] = ncon;

@@ -274,6 +274,7 @@ struct BodyRec {
   bool has_inertial = false;
   double ipos[3] = {0, 0, 0}, iquat[4] = {1, 0, 0, 0}, mass = 0, inertia[3] = {0, 0, 0};
   double gravcomp = 0;
+  bool mocap = false;
   std::vector<JointRec> joints;
   std::vector<GeomRec> geoms;
   std::vector<SiteRec> sites;
@@ -817,7 +818,11 @@ struct Compiler {
     get_orientation(e, nullptr, "body", b.quat);
     frame.apply(b.pos, b.quat);
     if (auto* s = e->attr("gravcomp")) b.gravcomp = parse_reals(*s, e, "gravcomp").at(0);
-    if (e->attr("mocap") && *e->attr("mocap") == "true") fail(e, "mocap bodies are not supported");
+    if (auto* s = e->attr("mocap")) {
+      if (*s != "true" && *s != "false") fail(e, "attribute 'mocap' must be true/false");
+      b.mocap = *s == "true";
+    }
+    if (b.mocap && parent != 0) fail(e, "mocap body must be a child of the world");
     int id = static_cast<int>(bodies.size());
     bodies.push_back(b);
     parse_body_children(e, id, childclass, Frame(), suffix);
@@ -1009,6 +1014,9 @@ struct Compiler {
     for (int b = 0; b < static_cast<int>(bodies.size()); ++b)
       for (const LightRec& l : bodies[b].lights) {
         if (m.body_weldid[b] != 0) throw std::runtime_error("MJCF error: lights on moving bodies are not supported");
+        // (a mocap body is welded to the world, yet its pose is per-env state)
+        if (m.body_mocapid[m.body_rootid[b]] >= 0)
+          throw std::runtime_error("MJCF error: lights on or below mocap bodies are not supported");
         double p[3], d[3];
         rot_vec_quat(p, l.pos, &x0quat[4 * b]);
         for (int i = 0; i < 3; ++i) p[i] += x0pos[3 * b + i];
@@ -1315,6 +1323,14 @@ struct Compiler {
       const XmlElement* e = cp.get();
       if (e->tag != "key") fail(e, "unsupported keyframe element");
       std::vector<double> qpos = m.qpos0, qvel(m.nv, 0.0), ctrl(m.nu, 0.0), act(m.na, 0.0);
+      // mocap poses default to the bodies' pos / quat (mj_resetData's mocap_pos / mocap_quat)
+      std::vector<double> mpos(3 * m.nmocap), mquat(4 * m.nmocap);
+      for (int b = 0; b < m.nbody; ++b) {
+        const int id = m.body_mocapid[b];
+        if (id < 0) continue;
+        std::copy(&m.body_pos[3 * b], &m.body_pos[3 * b] + 3, &mpos[3 * id]);
+        std::copy(&m.body_quat[4 * b], &m.body_quat[4 * b] + 4, &mquat[4 * id]);
+      }
       double time = 0;
       if (auto* s = e->attr("time")) time = parse_reals(*s, e, "time").at(0);
       auto fill = [&](const char* key, std::vector<double>& dst) {
@@ -1328,11 +1344,15 @@ struct Compiler {
       fill("qvel", qvel);
       fill("ctrl", ctrl);
       fill("act", act);
+      fill("mpos", mpos);
+      fill("mquat", mquat);
       m.key_time.push_back(time);
       m.key_qpos.insert(m.key_qpos.end(), qpos.begin(), qpos.end());
       m.key_qvel.insert(m.key_qvel.end(), qvel.begin(), qvel.end());
       m.key_ctrl.insert(m.key_ctrl.end(), ctrl.begin(), ctrl.end());
       m.key_act.insert(m.key_act.end(), act.begin(), act.end());
+      m.key_mpos.insert(m.key_mpos.end(), mpos.begin(), mpos.end());
+      m.key_mquat.insert(m.key_mquat.end(), mquat.begin(), mquat.end());
       ++m.nkey;
     }
   }
@@ -1377,6 +1397,8 @@ struct Compiler {
       quat_normalize(B.quat);
       m.body_quat.insert(m.body_quat.end(), B.quat, B.quat + 4);
       m.body_gravcomp.push_back(B.gravcomp);
+      if (B.mocap && !B.joints.empty()) fail(nullptr, "mocap body '" + B.name + "' cannot have joints");
+      m.body_mocapid.push_back(B.mocap ? m.nmocap++ : -1);
       // joints and dofs
       m.body_jntadr.push_back(B.joints.empty() ? -1 : m.njnt);
       m.body_jntnum.push_back(static_cast<int>(B.joints.size()));
@@ -2399,6 +2421,8 @@ mrs_model_view Model::view() const {
   MRS_V(site_type); MRS_V(site_size);
   MRS_V(actuator_actadr); MRS_V(actuator_actnum); MRS_V(actuator_actlimited); MRS_V(actuator_actearly);
   MRS_V(actuator_dynprm); MRS_V(actuator_actrange); MRS_V(key_act);
+  v.nmocap = nmocap;
+  MRS_V(body_mocapid); MRS_V(key_mpos); MRS_V(key_mquat);
 #undef MRS_V
   return v;
 }

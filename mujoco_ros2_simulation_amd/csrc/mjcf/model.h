@@ -53,6 +53,10 @@ struct Model {
   // activation state (mrs_model_view actuator_act* / actuator_dynprm): na stateful actuators
   std::vector<int> actuator_actadr, actuator_actnum, actuator_actlimited, actuator_actearly;
   std::vector<double> actuator_dynprm, actuator_actrange, key_act;
+  // mocap bodies (mrs_model_view nmocap / body_mocapid / key_mpos / key_mquat)
+  int nmocap = 0;
+  std::vector<int> body_mocapid;
+  std::vector<double> key_mpos, key_mquat;
 
   std::vector<int> sensor_type, sensor_objtype, sensor_objid, sensor_dim, sensor_adr;
   std::vector<double> sensor_cutoff;

@@ -7,7 +7,7 @@
 // are mjModel's: m->nq, m->jnt_qposadr[j], m->sensor_adr[s], ...) plus mjOption under m->opt; it
 // owns a private copy of the compiled model, so a copy outlives the plugin exactly as
 // mj_copyModel's does.  mjData holds the host mirror of one environment's state arrays under
-// mjData's names, in one allocation (xfrc_applied and act, appended after the first members, lie in it too).  The five lifecycle functions keep MuJoCo's names and
+// mjData's names, in one allocation (xfrc_applied, act and the mocap poses, appended after the first members, lie in it too).  The five lifecycle functions keep MuJoCo's names and
 // argument conventions (dest == nullptr allocates); they are this library's own.
 #pragma once
 
@@ -44,6 +44,9 @@ struct mjData_ {
   int nbody;
   double* act;                  // na: activations of the stateful actuators (m->actuator_actadr[i], -1 none)
   int na;
+  double* mocap_pos;            // 3 * nmocap: world positions of the mocap bodies (m->body_mocapid[b], -1 none)
+  double* mocap_quat;           // 4 * nmocap: their orientations (normalised where the kinematics read them)
+  int nmocap;
 };
 typedef struct mjData_ mjData;
 
@@ -52,7 +55,7 @@ mjModel* mj_wrapModel(mrs_model* handle);
 // deep copy of src into dest (dest == nullptr: a new mjModel); returns dest
 mjModel* mj_copyModel(mjModel* dest, const mjModel* src);
 void mj_deleteModel(mjModel* m);
-// zero-initialised mjData sized for m
+// zero-initialised mjData sized for m (the mocap poses at the bodies' pos / quat, as mj_resetData's)
 mjData* mj_makeData(const mjModel* m);
 // copy every array and the time of src into dest (dest == nullptr: a new mjData); returns dest,
 // nullptr if dest and src were made for different sizes

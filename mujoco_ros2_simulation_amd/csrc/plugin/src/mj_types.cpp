@@ -60,8 +60,9 @@ mjData* mj_makeData(const mjModel* m) {
   d->nsensordata = m->nsensordata;
   d->nbody = m->nbody;
   d->na = m->na;
+  d->nmocap = m->nmocap;
   const size_t n = size_t(d->nq) + 5 * size_t(d->nv) + size_t(d->nu) + size_t(d->nsensordata) + 6 * size_t(d->nbody) +
-                   size_t(d->na);
+                   size_t(d->na) + 7 * size_t(d->nmocap);
   d->buffer = new double[n > 0 ? n : 1]();
   double* p = d->buffer;
   auto take = [&p](int k) { double* r = p; p += k; return r; };
@@ -75,20 +76,28 @@ mjData* mj_makeData(const mjModel* m) {
   d->sensordata = take(d->nsensordata);
   d->xfrc_applied = take(6 * d->nbody);
   d->act = take(d->na);
+  d->mocap_pos = take(3 * d->nmocap);
+  d->mocap_quat = take(4 * d->nmocap);
+  for (int b = 0; b < m->nbody && d->nmocap > 0; ++b) {
+    const int id = m->body_mocapid[b];
+    if (id < 0) continue;
+    std::memcpy(d->mocap_pos + 3 * id, m->body_pos + 3 * b, 3 * sizeof(double));
+    std::memcpy(d->mocap_quat + 4 * id, m->body_quat + 4 * b, 4 * sizeof(double));
+  }
   return d;
 }
 
 mjData* mj_copyData(mjData* dest, const mjModel* m, const mjData* src) {
   if (!m || !src) return nullptr;
   if (src->nq != m->nq || src->nv != m->nv || src->nu != m->nu || src->nsensordata != m->nsensordata ||
-      src->nbody != m->nbody || src->na != m->na)
+      src->nbody != m->nbody || src->na != m->na || src->nmocap != m->nmocap)
     return nullptr;
   if (!dest) dest = mj_makeData(m);
   else if (dest->nq != m->nq || dest->nv != m->nv || dest->nu != m->nu || dest->nsensordata != m->nsensordata ||
-           dest->nbody != m->nbody || dest->na != m->na)
+           dest->nbody != m->nbody || dest->na != m->na || dest->nmocap != m->nmocap)
     return nullptr;
   const size_t n = size_t(m->nq) + 5 * size_t(m->nv) + size_t(m->nu) + size_t(m->nsensordata) + 6 * size_t(m->nbody) +
-                   size_t(m->na);
+                   size_t(m->na) + 7 * size_t(m->nmocap);
   if (dest != src) std::memcpy(dest->buffer, src->buffer, n * sizeof(double));
   dest->time = src->time;
   return dest;

@@ -622,6 +622,7 @@ void MujocoSystemInterface::pull_state_locked() {
     mrs_batch_get_field(batch_, MRS_FIELD_QACC_WARMSTART, mj_data_->qacc_warmstart, 0, 1);
   }
   if (view_.na > 0) mrs_batch_get_act(batch_, mj_data_->act, 0, 1);
+  if (view_.nmocap > 0) mrs_batch_get_mocap(batch_, mj_data_->mocap_pos, mj_data_->mocap_quat, 0, 1);
   mrs_batch_get_field(batch_, MRS_FIELD_TIME, &mj_data_->time, 0, 1);
   // sim -> control copy of the outputs (mj_copyData(control <- sim), reference :1759); the control
   // inputs ctrl / qfrc_applied stay what write() put there
@@ -635,6 +636,8 @@ void MujocoSystemInterface::pull_state_locked() {
   std::copy(d.sensordata, d.sensordata + d.nsensordata, c.sensordata);
   std::copy(d.xfrc_applied, d.xfrc_applied + 6 * d.nbody, c.xfrc_applied);
   std::copy(d.act, d.act + d.na, c.act);
+  std::copy(d.mocap_pos, d.mocap_pos + 3 * d.nmocap, c.mocap_pos);
+  std::copy(d.mocap_quat, d.mocap_quat + 4 * d.nmocap, c.mocap_quat);
   c.time = d.time;
 }
 
@@ -764,6 +767,7 @@ void MujocoSystemInterface::set_data(mjData* mj_data) {
   push_xfrc_locked();
   if (view_.nu > 0) mrs_batch_set_field(batch_, MRS_FIELD_CTRL, mj_data_->ctrl, 0, 1);
   if (view_.na > 0) mrs_batch_set_act(batch_, mj_data_->act, 0, 1);
+  if (view_.nmocap > 0) mrs_batch_set_mocap(batch_, mj_data_->mocap_pos, mj_data_->mocap_quat, 0, 1);
   mrs_batch_set_field(batch_, MRS_FIELD_TIME, &mj_data_->time, 0, 1);
   mrs_batch_forward(batch_);
   mrs_batch_sync(batch_);

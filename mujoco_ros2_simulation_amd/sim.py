@@ -158,6 +158,11 @@ _ACT_ARRAYS = [
     ("key_act", "d", "nkey", "na"),
 ]
 DYN_NONE, DYN_INTEGRATOR, DYN_FILTER, DYN_FILTEREXACT = range(4)
+# mocap bodies (after the activation block): nmocap, then body_mocapid and the keyframes' poses; a
+# width (name, k) is k times that size
+_MOCAP_SIZES = ["nmocap"]
+_MOCAP_ARRAYS = [("body_mocapid", "i", "nbody", 1), ("key_mpos", "d", "nkey", ("nmocap", 3)),
+                 ("key_mquat", "d", "nkey", ("nmocap", 4))]
 
 
 class ModelView(C.Structure):
@@ -182,7 +187,9 @@ class ModelView(C.Structure):
                 [(n, C.c_int) for n in _POLY_SIZES] +
                 [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _POLY_ARRAYS] +
                 [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _SITE_ARRAYS] +
-                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _ACT_ARRAYS])
+                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _ACT_ARRAYS] +
+                [(n, C.c_int) for n in _MOCAP_SIZES] +
+                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _MOCAP_ARRAYS])
 
 
 _lib = None
@@ -227,6 +234,12 @@ def lib() -> C.CDLL:
         L.mrs_batch_get_act.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.mrs_batch_act_device_ptr.restype = C.c_void_p
         L.mrs_batch_act_device_ptr.argtypes = [C.c_void_p]
+        L.mrs_batch_set_mocap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.mrs_batch_get_mocap.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.mrs_batch_mocap_pos_device_ptr.restype = C.c_void_p
+        L.mrs_batch_mocap_pos_device_ptr.argtypes = [C.c_void_p]
+        L.mrs_batch_mocap_quat_device_ptr.restype = C.c_void_p
+        L.mrs_batch_mocap_quat_device_ptr.argtypes = [C.c_void_p]
         L.mrs_batch_set_ctrl_device.argtypes = [C.c_void_p, C.c_void_p]
         L.mrs_batch_bind_ctrl_device.argtypes = [C.c_void_p, C.c_void_p]
         L.mrs_batch_set_timing.argtypes = [C.c_void_p, C.c_int]
@@ -281,7 +294,7 @@ class Model:
         self.view = ModelView()
         _check(lib().mrs_model_view_get(self._h, C.byref(self.view)))
         v = self.view
-        for n in _SIZES + _MESH_SIZES + _CONTACT_SIZES + _EQ_SIZES + _REND_SIZES + _TEN_SIZES + _POLY_SIZES:
+        for n in _SIZES + _MESH_SIZES + _CONTACT_SIZES + _EQ_SIZES + _REND_SIZES + _TEN_SIZES + _POLY_SIZES + _MOCAP_SIZES:
             setattr(self, n, getattr(v, n))
         for n in ["timestep", "tolerance", "impratio", "ls_tolerance", "ls_iterations", "restate", "integrator", "solver",
                   "iterations", "disableflags",
@@ -290,17 +303,21 @@ class Model:
         self.gravity = np.array(v.gravity[:])
         self.vis_headlight = np.array(v.vis_headlight[:])
         for name, kind, count, width in (_ARRAYS + _MESH_ARRAYS + _CONTACT_ARRAYS + _EQ_ARRAYS + _REND_ARRAYS +
-                                         _TEN_ARRAYS + _POLY_ARRAYS + _SITE_ARRAYS + _ACT_ARRAYS):
+                                         _TEN_ARRAYS + _POLY_ARRAYS + _SITE_ARRAYS + _ACT_ARRAYS +
+                                         _MOCAP_ARRAYS):
             n = getattr(v, count)
-            w = getattr(v, width) if isinstance(width, str) else width
+            if isinstance(width, tuple):
+                w = getattr(v, width[0]) * width[1]
+            else:
+                w = getattr(v, width) if isinstance(width, str) else width
             ptr = getattr(v, name)
             size = n * w
             if size == 0 or not ptr:
-                arr = np.zeros((n, w) if (w > 1 or isinstance(width, str)) else (n,),
+                arr = np.zeros((n, w) if (w > 1 or not isinstance(width, int)) else (n,),
                                dtype=np.int32 if kind == "i" else np.float64)
             else:
                 arr = np.ctypeslib.as_array(ptr, shape=(size,)).copy()
-                if w > 1 or isinstance(width, str):
+                if w > 1 or not isinstance(width, int):
                     arr = arr.reshape(n, w)
             setattr(self, name, arr)
 
@@ -408,6 +425,37 @@ class Batch:
     def act_device_ptr(self) -> int:
         """the activations on the device, fp32 [n, na], ordered on the batch stream (0 when na == 0)"""
         return lib().mrs_batch_act_device_ptr(self._h) or 0
+
+    def get_mocap(self, env0: int = 0, n: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """mjData.mocap_pos [n, nmocap, 3] and mocap_quat [n, nmocap, 4] as the caller wrote them (the
+        kernel normalises the quaternion it reads); rows by body_mocapid"""
+        n = self.n - env0 if n is None else n
+        nm = self.model.nmocap
+        pos = np.empty((n, nm, 3), dtype=np.float64)
+        quat = np.empty((n, nm, 4), dtype=np.float64)
+        _check(lib().mrs_batch_get_mocap(self._h, pos.ctypes.data, quat.ctypes.data, env0, n))
+        return pos, quat
+
+    def set_mocap(self, pos=None, quat=None, env0: int = 0) -> None:
+        """write the mocap poses of envs [env0, env0 + n); a part given as None is left as it is"""
+        nm = self.model.nmocap
+        if nm == 0 or (pos is None and quat is None):
+            return
+        p = None if pos is None else np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, nm, 3)
+        q = None if quat is None else np.ascontiguousarray(quat, dtype=np.float64).reshape(-1, nm, 4)
+        if p is not None and q is not None and p.shape[0] != q.shape[0]:
+            raise ValueError("pos and quat cover different numbers of envs")
+        n = (p if p is not None else q).shape[0]
+        _check(lib().mrs_batch_set_mocap(self._h, None if p is None else p.ctypes.data,
+                                         None if q is None else q.ctypes.data, env0, n))
+
+    def mocap_pos_device_ptr(self) -> int:
+        """mocap_pos on the device, fp32 [n, nmocap, 3], ordered on the batch stream (0 when nmocap == 0)"""
+        return lib().mrs_batch_mocap_pos_device_ptr(self._h) or 0
+
+    def mocap_quat_device_ptr(self) -> int:
+        """mocap_quat on the device, fp32 [n, nmocap, 4] (0 when nmocap == 0)"""
+        return lib().mrs_batch_mocap_quat_device_ptr(self._h) or 0
 
     def reset(self, key: int = -1, env0: int = 0, n: int | None = None) -> None:
         _check(lib().mrs_batch_reset(self._h, key, env0, self.n - env0 if n is None else n))
