@@ -188,6 +188,41 @@ int mrs_batch_get_mocap(mrs_batch* b, double* pos, double* quat, int env0, int n
 float* mrs_batch_mocap_pos_device_ptr(mrs_batch* b);
 float* mrs_batch_mocap_quat_device_ptr(mrs_batch* b);
 
+/* ---- per-env model parameters (no reference counterpart: the reference steps one mjData of one
+ * mjModel; here every env of a batch may carry its own values of the mjModel attributes that domain
+ * randomisation draws most and that have no derived constants in the compiled model, so writing them is
+ * exactly compiling the scene with those attributes changed).  Not MRS_FIELD_* values. */
+enum {
+  MRS_PARAM_ACT_GAINPRM = 0,   /* [nu][3]  mjModel.actuator_gainprm[:, 0:3] */
+  MRS_PARAM_ACT_BIASPRM = 1,   /* [nu][3]  mjModel.actuator_biasprm[:, 0:3] */
+  MRS_PARAM_DOF_DAMPING = 2,   /* [nv] */
+  MRS_PARAM_GEOM_FRICTION = 3, /* [ngeom]  sliding coefficient only */
+  MRS_PARAM_COUNT = 4
+};
+/* floats per env of a parameter (3 nu, 3 nu, nv, ngeom), < 0 on error */
+int mrs_batch_param_dim(const mrs_batch* b, int param);
+/* host rows [n][dim] fp64 for envs [env0, env0+n).  A parameter's buffer is made on the first
+ * set_param / param_device_ptr of that parameter, every env filled with the model's own fp32 values;
+ * before that get_param returns the model's values for every env and the launches take none of the
+ * per-env code for that parameter.  Model values, not data values: mrs_batch_reset, both masked resets
+ * and the NaN auto-reset leave them untouched.  The values hold over the n steps of a launch and over
+ * RK4's stages.  The actuator's gaintype / biastype stay the model's: a fixed gain ignores
+ * gainprm[1:3], bias type none ignores all of biasprm.  A position actuator's kp lives in both
+ * gainprm[0] and -biasprm[1] (and kv in -biasprm[2]); as with mjModel, keeping them consistent is the
+ * caller's job.  Friction: an automatic pair's sliding friction is max of its two geoms' per-env values
+ * (mj_contactParam with equal priorities); explicit <contact><pair> entries keep the pair's own;
+ * torsional and rolling friction stay the model's.  The one exception to "a write equals compiling the
+ * scene with the attribute changed": an explicit pair written without friction= took max of its geoms'
+ * friction when the model was compiled, and keeps that compiled value -- it does not follow the per-env
+ * geom values.  set_param rejects a bad param, env0 or n, non-finite
+ * values, and negative damping or friction with MRS_ERR_INVALID (nothing is written then). */
+int mrs_batch_set_param(mrs_batch* b, int param, const double* host, int env0, int n);
+int mrs_batch_get_param(mrs_batch* b, int param, double* host, int env0, int n);
+/* device pointer of a parameter's buffer, [n_envs][dim] fp32 (made by this call if need be); a write
+ * ordered on the batch stream takes effect at the next step / forward launch.  Writes through it are not
+ * checked.  NULL when dim == 0 or on error (mrs_last_status). */
+float* mrs_batch_param_device_ptr(mrs_batch* b, int param);
+
 /* replaces mj_step (src/mujoco_system_interface.cpp:1691,1731): advance every env n_steps times,
  * fused in one launch; ctrl / qfrc_applied are held constant (zero-order hold) across the n steps,
  * exactly as PhysicsLoop holds them between write() calls.  Asynchronous on the batch stream.

@@ -22,8 +22,16 @@ HIP_SOURCES = ["hip/step.hip", "hip/batch.hip"]
 # others each instantiate one group width's kernels (17: the G = 16 primal-solver kernel; 18 / 65: the
 # G = 16 / 64 kernels with the extended code, MRS_EXT -- MPR contact polish, > 32 ray geoms -- which
 # parts 16, 17, 19 and 64 leave out; 19: the G = 16 step kernels with ray helper waves)
-STEP_PARTS = [0, 8, 16, 17, 18, 19, 32, 64, 65]
-STEP_NO_EXT = {16, 17, 19, 64}
+# 108 / 116 / 120 / 132 / 164: the G = 8 / 16 / 16 with helper waves / 32 / 64 kernels with the per-env
+# model parameter reads (MRS_PRM), launched only by batches that use one; every other part leaves them out
+STEP_PARTS = [0, 8, 16, 17, 18, 19, 32, 64, 65, 108, 116, 120, 132, 164]
+STEP_NO_EXT = {16, 17, 19, 64, 120}
+STEP_PRM = {108, 116, 120, 132, 164}
+
+
+def _part_flags(part: int) -> list[str]:
+    return [f"-DMRS_STEP_PART={part}", f"-DMRS_EXT={0 if part in STEP_NO_EXT else 1}",
+            f"-DMRS_PRM={1 if part in STEP_PRM else 0}"]
 # fp32 division/sqrt via v_rcp/v_sqrt (<= 2.5 ulp) instead of the correctly-rounded sequences:
 # the parity tolerance is 1e-5 relative, and the ray/contact math is division-heavy
 HIP_FLAGS = ["-fno-hip-fp32-correctly-rounded-divide-sqrt",
@@ -72,7 +80,7 @@ def build_lib(verbose: bool = False) -> Path:
         if not _newer(src, obj, deps):
             continue
         if rel.endswith(".hip"):
-            extra = [f"-DMRS_STEP_PART={part}", f"-DMRS_EXT={0 if part in STEP_NO_EXT else 1}"] if part is not None else []
+            extra = _part_flags(part) if part is not None else []
             cmd = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", *HIP_FLAGS, *extra, "-c", str(src),
                    "-o", str(obj)]
         else:
@@ -108,7 +116,7 @@ def build_variant(name: str, flags: list[str]) -> Path:
     for part in parts:
         obj = vdir / f"step.part{part}.o"
         objs.append(obj)
-        pflags = [] if part is None else [f"-DMRS_STEP_PART={part}", f"-DMRS_EXT={0 if part in STEP_NO_EXT else 1}"]
+        pflags = [] if part is None else _part_flags(part)
         cmd = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", *HIP_FLAGS, *pflags,
                *flags, "-c", str(src), "-o", str(obj)]
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

@@ -294,6 +294,39 @@ int mrs_batch_get_mocap(mrs_batch* b, double* pos, double* quat, int env0, int n
 float* mrs_batch_mocap_pos_device_ptr(mrs_batch* b) { return b ? mrs::batch_mocap_pos_device_ptr(b->impl) : nullptr; }
 float* mrs_batch_mocap_quat_device_ptr(mrs_batch* b) { return b ? mrs::batch_mocap_quat_device_ptr(b->impl) : nullptr; }
 
+int mrs_batch_param_dim(const mrs_batch* b, int param) {
+  int dim = MRS_ERR_INVALID;
+  const int rc = guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    dim = mrs::batch_param_dim(b->impl, param);
+  });
+  return rc == MRS_OK ? dim : rc;
+}
+
+int mrs_batch_set_param(mrs_batch* b, int param, const double* host, int env0, int n) {
+  return guarded([&] {
+    if (!b || !host) throw std::invalid_argument("null argument");
+    mrs::batch_set_param(b->impl, param, host, env0, n);
+  });
+}
+
+int mrs_batch_get_param(mrs_batch* b, int param, double* host, int env0, int n) {
+  return guarded([&] {
+    if (!b || !host) throw std::invalid_argument("null argument");
+    mrs::batch_get_param(b->impl, param, host, env0, n);
+  });
+}
+
+float* mrs_batch_param_device_ptr(mrs_batch* b, int param) {
+  // (the buffer is made on first use, which can fail: NULL then, the code in mrs_last_status)
+  float* p = nullptr;
+  guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    p = mrs::batch_param_device_ptr(b->impl, param);
+  });
+  return p;
+}
+
 int mrs_batch_step(mrs_batch* b, int n_steps) {
   return guarded([&] {
     if (!b) throw std::invalid_argument("null batch");

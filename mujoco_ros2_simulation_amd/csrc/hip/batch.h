@@ -36,6 +36,12 @@ void batch_set_mocap(BatchImpl* b, const double* pos, const double* quat, int en
 void batch_get_mocap(BatchImpl* b, double* pos, double* quat, int env0, int n);
 float* batch_mocap_pos_device_ptr(BatchImpl* b);   // null when nmocap == 0
 float* batch_mocap_quat_device_ptr(BatchImpl* b);  // null when nmocap == 0
+// per-env model parameters (MRS_PARAM_*): floats per env (throws on a bad param), host rows [n][dim],
+// and the device buffer [n_envs][dim], made on the first set / device_ptr (null when dim == 0)
+int batch_param_dim(const BatchImpl* b, int param);
+void batch_set_param(BatchImpl* b, int param, const double* host, int env0, int n);
+void batch_get_param(BatchImpl* b, int param, double* host, int env0, int n);
+float* batch_param_device_ptr(BatchImpl* b, int param);
 void batch_set_ctrl_device(BatchImpl* b, const float* d_ctrl);
 void batch_bind_ctrl_device(BatchImpl* b, const float* d_ctrl);  // zero-copy ctrl source (null: own buffer)
 void batch_set_timing(BatchImpl* b, int mask);  // launches timed for batch_last_kernel_ms (bit 0 step, 1 frames)

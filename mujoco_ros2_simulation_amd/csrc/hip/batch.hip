@@ -24,7 +24,7 @@
 namespace mrs {
 
 hipError_t launch_step(const DevModel* d_model, int lds_floats, int shared_floats, const DevState& st, int n_envs,
-                       int n_steps, bool forward_only, int group, bool primal, bool ext, hipStream_t stream);
+                       int n_steps, bool forward_only, int group, bool primal, bool ext, bool params, hipStream_t stream);
 
 namespace {
 
@@ -1281,6 +1281,7 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
       }
   }
   d.npair = static_cast<int>(pg1.size());
+  d.npair_explicit = static_cast<int>(m.expair_geom1.size());
   b.pair_g1 = pg1;
   // active equality constraints (rows first in the solver order, as mj_makeConstraint)
   std::vector<int> eq_t, eq_o1, eq_o2;
@@ -2319,6 +2320,59 @@ float* ensure_xfrc(BatchImpl& b) {
   }
   return b.st.xfrc_applied;
 }
+// per-env model parameters (MRS_PARAM_*): floats per env, -1 for an unknown parameter
+int param_dim(const Model& m, int param) {
+  switch (param) {
+    case MRS_PARAM_ACT_GAINPRM: case MRS_PARAM_ACT_BIASPRM: return 3 * m.nu;
+    case MRS_PARAM_DOF_DAMPING: return m.nv;
+    case MRS_PARAM_GEOM_FRICTION: return m.ngeom;
+  }
+  return -1;
+}
+// the model's own row of a parameter, in the fp32 rounding the kernel's tables hold (actrec, dofrec,
+// pair_friction)
+std::vector<float> param_model_row(const Model& m, int param) {
+  std::vector<float> r(static_cast<size_t>(std::max(0, param_dim(m, param))));
+  for (size_t i = 0; i < r.size(); ++i) {
+    switch (param) {
+      case MRS_PARAM_ACT_GAINPRM: r[i] = static_cast<float>(m.actuator_gainprm[MRS_NGAIN * (i / 3) + i % 3]); break;
+      case MRS_PARAM_ACT_BIASPRM: r[i] = static_cast<float>(m.actuator_biasprm[MRS_NBIAS * (i / 3) + i % 3]); break;
+      case MRS_PARAM_DOF_DAMPING: r[i] = static_cast<float>(m.dof_damping[i]); break;
+      case MRS_PARAM_GEOM_FRICTION: r[i] = static_cast<float>(m.geom_friction[3 * i]); break;
+    }
+  }
+  return r;
+}
+const float*& param_slot(BatchImpl& b, int param) {
+  switch (param) {
+    case MRS_PARAM_ACT_GAINPRM: return b.dm.prm_gain;
+    case MRS_PARAM_ACT_BIASPRM: return b.dm.prm_bias;
+    case MRS_PARAM_DOF_DAMPING: return b.dm.prm_damp;
+    default: return b.dm.prm_fric;
+  }
+}
+// a parameter's buffer [n][dim], made when the parameter is first used and filled with the model's own
+// values for every env; from then on the step kernel reads it (DevModel::prm_*).  Like ensure_xfrc:
+// the earlier launches have finished before the model block changes.  Null when dim == 0
+float* ensure_param(BatchImpl& b, int param) {
+  const int dim = param_dim(*b.model, param);
+  if (dim < 0) throw std::invalid_argument("unknown model parameter");
+  if (dim == 0) return nullptr;
+  const float*& slot = param_slot(b, param);
+  if (!slot) {
+    HIP_CHECK(hipSetDevice(b.device));
+    const std::vector<float> row = param_model_row(*b.model, param);
+    std::vector<float> all(static_cast<size_t>(b.n) * dim);
+    for (int e = 0; e < b.n; ++e) std::copy(row.begin(), row.end(), all.begin() + static_cast<size_t>(e) * dim);
+    float* p = static_cast<float*>(dalloc(b, all.size() * sizeof(float)));
+    HIP_CHECK(hipStreamSynchronize(b.stream));
+    HIP_CHECK(hipMemcpy(p, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
+    slot = p;
+    b.dm.prm_mask |= 1 << param;
+    HIP_CHECK(hipMemcpy(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice));
+  }
+  return const_cast<float*>(slot);
+}
 void* field_ptr(BatchImpl& b, int field) {
   switch (field) {
     case MRS_FIELD_QPOS: return b.st.qpos;
@@ -2464,7 +2518,7 @@ BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_cont
       prod.rf_sweep = 0;  // (the producer pass is a block pass over the static geoms)
       DevModel* d_prod = static_cast<DevModel*>(dalloc(*b, sizeof(DevModel)));
       HIP_CHECK(hipMemcpyAsync(d_prod, &prod, sizeof(DevModel), hipMemcpyHostToDevice, b->stream));
-      HIP_CHECK(launch_step(d_prod, b->L.total, b->dm.shr_total, b->st, 1, 1, true, b->group, false, b->ext, b->stream));
+      HIP_CHECK(launch_step(d_prod, b->L.total, b->dm.shr_total, b->st, 1, 1, true, b->group, false, b->ext, false, b->stream));
       HIP_CHECK(hipStreamSynchronize(b->stream));
     }
     batch_launch(b, 1, true);  // mj_forward after load (src/mujoco_system_interface.cpp:741)
@@ -2777,6 +2831,54 @@ void batch_get_mocap(BatchImpl* b, double* pos, double* quat, int env0, int n) {
 float* batch_mocap_pos_device_ptr(BatchImpl* b) { return b->dm.mocap_pos; }
 float* batch_mocap_quat_device_ptr(BatchImpl* b) { return b->dm.mocap_quat; }
 
+int batch_param_dim(const BatchImpl* b, int param) {
+  const int dim = param_dim(*b->model, param);
+  if (dim < 0) throw std::invalid_argument("unknown model parameter");
+  return dim;
+}
+
+void batch_set_param(BatchImpl* b, int param, const double* host, int env0, int n) {
+  const int dim = batch_param_dim(b, param);
+  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
+  if (n == 0 || dim == 0) return;
+  const size_t cnt = static_cast<size_t>(n) * dim;
+  // checked before anything is made or written: finite, and no negative damping or friction
+  const bool nonneg = param == MRS_PARAM_DOF_DAMPING || param == MRS_PARAM_GEOM_FRICTION;
+  std::vector<float> tmp(cnt);
+  for (size_t i = 0; i < cnt; ++i) {
+    tmp[i] = static_cast<float>(host[i]);
+    if (!std::isfinite(host[i]) || !std::isfinite(tmp[i])) throw std::invalid_argument("model parameter value is not finite");
+    if (nonneg && host[i] < 0) throw std::invalid_argument("negative damping or friction");
+  }
+  HIP_CHECK(hipSetDevice(b->device));
+  float* dst = ensure_param(*b, param);
+  HIP_CHECK(hipMemcpyAsync(dst + static_cast<size_t>(env0) * dim, tmp.data(), cnt * sizeof(float), hipMemcpyHostToDevice,
+                           b->stream));
+  HIP_CHECK(hipStreamSynchronize(b->stream));
+}
+
+void batch_get_param(BatchImpl* b, int param, double* host, int env0, int n) {
+  const int dim = batch_param_dim(b, param);
+  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
+  if (n == 0 || dim == 0) return;
+  const float* src = param_slot(*b, param);
+  if (!src) {  // never used: the model's values for every env, and no buffer made
+    const std::vector<float> row = param_model_row(*b->model, param);
+    for (int e = 0; e < n; ++e)
+      for (int i = 0; i < dim; ++i) host[static_cast<size_t>(e) * dim + i] = row[i];
+    return;
+  }
+  HIP_CHECK(hipSetDevice(b->device));
+  const size_t cnt = static_cast<size_t>(n) * dim;
+  std::vector<float> tmp(cnt);
+  HIP_CHECK(hipMemcpyAsync(tmp.data(), src + static_cast<size_t>(env0) * dim, cnt * sizeof(float), hipMemcpyDeviceToHost,
+                           b->stream));
+  HIP_CHECK(hipStreamSynchronize(b->stream));
+  for (size_t i = 0; i < cnt; ++i) host[i] = tmp[i];
+}
+
+float* batch_param_device_ptr(BatchImpl* b, int param) { return ensure_param(*b, param); }
+
 void batch_bind_ctrl_device(BatchImpl* b, const float* d_ctrl) { b->ctrl_bound = d_ctrl; }
 
 void batch_set_timing(BatchImpl* b, int mask) {
@@ -2802,7 +2904,7 @@ void batch_launch(BatchImpl* b, int n_steps, bool forward_only) {
   DevState st = b->st;
   if (b->ctrl_bound) st.ctrl = const_cast<float*>(b->ctrl_bound);  // (read only: loaded at launch start)
   HIP_CHECK(launch_step(b->d_dm, b->L.total, b->dm.shr_total, st, b->n, n_steps, forward_only, b->group,
-                        b->model->solver != MRS_SOL_PGS, b->ext, b->stream));
+                        b->model->solver != MRS_SOL_PGS, b->ext, b->dm.prm_mask != 0, b->stream));
   if (timed) HIP_CHECK(hipEventRecord(b->ev1[0], b->stream));
   b->ev_valid[0] = timed;
 }

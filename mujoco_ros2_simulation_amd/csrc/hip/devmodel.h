@@ -71,7 +71,8 @@ struct ScratchLayout {
       efc_fd,                // elliptic models: the PGS row forces in fp64 (2 floats per row)
       sens,                  // sensordata sink of idle lane groups (envs past n_envs)
       efc_n,                 // rows of the dense layout of the last forward (int bits; -1: none stored)
-      xfrc;                  // the lane group's row of DevState::xfrc_applied (int bits; -1: an idle group, none)
+      xfrc;                  // the lane group's row of DevState::xfrc_applied and of the per-env model
+                             // parameters (DevModel::prm_*) (int bits; -1: an idle group, none)
   int total;
 };
 constexpr int kMaxPairCon = 8;  // contacts one geom pair can produce (box-box: the clipped face polygon)
@@ -235,6 +236,10 @@ struct DevModel {
   // actuator dynamics, whose launches then take none of the activation code -- and the per-actuator
   // dynamics records (batch.hip actdyn, 8 floats each; packed only when na > 0)
   int na;
+  // per-env model parameters in use (below): bit MRS_PARAM_* set once that parameter's buffer exists.
+  // Every read site tests this word, not the pointers: it sits beside na and xfrc, which the same
+  // phases load anyway, so a batch that sets no parameter pays a scalar bit test per site
+  int prm_mask;
   CPtr<float> actdyn;
   // mocap bodies (mjData.mocap_pos / mocap_quat): their count -- 0 for every model
   // without one, whose launches then take none of the mocap code -- and the batch's per-env poses, input
@@ -243,8 +248,20 @@ struct DevModel {
   // here, not in DevState, so the kernels' arguments are what they were
   int nmocap;
   float *mocap_pos, *mocap_quat;
+  // per-env model parameters (MRS_PARAM_*), each null until the parameter is first
+  // used (batch.hip ensure_param; its bit of prm_mask is set with it), so a batch that sets none takes
+  // none of the per-env code.  Plain global memory, fp32, filled with
+  // the model's own values: prm_gain / prm_bias [n_envs][nu][3] (gainprm / biasprm [0:3], what actrec
+  // [7..9] / [11..13] hold), prm_damp [n_envs][nv] (dofrec[9]), prm_fric [n_envs][ngeom] (the geoms'
+  // sliding friction; pair p >= npair_explicit mixes max of its two geoms', an explicit pair keeps
+  // pair_friction).  The lane group's row is the one xfrc_row uses (ScratchLayout::xfrc).  Never
+  // staged into the workgroup-shared tables, which are the same for every env
+  const float *prm_gain, *prm_bias, *prm_damp, *prm_fric;
+  int npair_explicit;  // the explicit <contact><pair> entries, first in the pair list
 };
 constexpr int kRayBlock = 128;
+// bits of DevModel::prm_mask (1 << MRS_PARAM_*)
+constexpr int kPrmGain = 1, kPrmBias = 2, kPrmDamp = 4, kPrmFric = 8;
 
 // waves per workgroup: 256-thread workgroups with lane groups (G < 64); one wave (one env) per
 // workgroup at G = 64, so LDS is granted per env (the C5 working set of ~13.5 KB fits 11 envs per

@@ -21,6 +21,13 @@
 #ifndef MRS_EXT
 #define MRS_EXT 1
 #endif
+// MRS_PRM: compile the per-env model parameter reads.  The split build compiles them
+// into parts of their own (MRS_PRM 1) that only batches with a parameter in use launch; every other
+// part is compiled with MRS_PRM 0 and carries none of that code, not even the tests (their call sites
+// alone cost C3 0.75 % in the G = 16 kernel, same-box A/B)
+#ifndef MRS_PRM
+#define MRS_PRM 1
+#endif
 
 namespace mrs {
 
@@ -2638,6 +2645,64 @@ __device__ __forceinline__ const gfloat* xfrc_row(const DevModel& m, const gfloa
   return row < 0 ? nullptr : (const gfloat*)m.xfrc + (size_t)row * 6 * m.nbody;
 }
 
+// ---- per-env model parameters (MRS_PARAM_*).  The functions that read them are out
+// of line and reached only behind the scalar test of their bit of DevModel::prm_mask, in the kernels built with
+// MRS_PRM (kPrm) only, which a batch launches once it has a parameter in use; so a batch
+// that sets none pays that branch alone.  The values come from global memory, row by the lane group's
+// env (the scratch slot xfrc_row reads; a mirror group its primary's row), never from the
+// workgroup-shared tables.  They take their arguments by value: a DevModel reference into an
+// out-of-line function would put the caller's whole model copy on the stack.
+
+constexpr bool kPrm = MRS_PRM != 0;
+// value i of the group's row of a parameter buffer [n_envs][dim]; an idle group (row -1) reads
+// nothing and keeps the model's `own`
+__device__ __forceinline__ float prm_at(const float* base, const gfloat* scr, int slot, int dim, int i, float own) {
+  const int row = __float_as_int(scr[slot]);
+  return row < 0 ? own : ((const gfloat*)base)[(size_t)row * dim + i];
+}
+__device__ float prm_env(const float* base, const gfloat* scr, int slot, int dim, int i, float own) {
+  return prm_at(base, scr, slot, dim, i, own);
+}
+// the affine gain (base = DevModel::prm_gain) or bias (prm_bias) of actuator a, prm[0] + prm[1] len +
+// prm[2] vel from its env's row (own0..2: the model's), in the statement form of smooth_forces' own
+__device__ float act_affine_env(const float* base, const gfloat* scr, int slot, int nu, int a, float own0, float own1,
+                                float own2, float len, float vel) {
+  const float p0 = prm_at(base, scr, slot, 3 * nu, 3 * a, own0);
+  const float p1 = prm_at(base, scr, slot, 3 * nu, 3 * a + 1, own1);
+  const float p2 = prm_at(base, scr, slot, 3 * nu, 3 * a + 2, own2);
+  return p0 + p1 * len + p2 * vel;
+}
+// sliding friction of pair p: max of its two geoms' per-env values (as batch.hip mixes pair_friction);
+// an explicit <contact><pair> (the first nexp pairs) keeps its own
+__device__ float pair_mu_env(const float* base, const gfloat* scr, int slot, int ngeom, int nexp, int p, int g1, int g2,
+                             float own) {
+  if (p < nexp) return own;
+  const int row = __float_as_int(scr[slot]);
+  if (row < 0) return own;
+  const gfloat* f = (const gfloat*)base + (size_t)row * ngeom;
+  return fmaxf(f[g1], f[g2]);
+}
+// the sliding friction coefficient of pair p: every read of pair_friction[3 * p] goes through here
+__device__ __forceinline__ float pair_mu(const DevModel& m, const gfloat* scr, int p) {
+  float mu = m.pair_friction[3 * p];
+  if (kPrm && (m.prm_mask & kPrmFric)) {
+    [[clang::noinline]] mu = pair_mu_env(m.prm_fric, scr, m.S.xfrc, m.ngeom, m.npair_explicit, p, m.pair_g1[p], m.pair_g2[p], mu);
+  }
+  return mu;
+}
+// the velocity coefficient of actuator a's gain (k = 0, actrec[9]) or bias (k = 1, actrec[13]) for the
+// integrators' derivative, and dof j's damping (dofrec[9])
+__device__ __forceinline__ float act_vel_coef(const DevModel& m, const gfloat* scr, int a, int k, float own) {
+  if (kPrm && (m.prm_mask & (k ? kPrmBias : kPrmGain))) {
+    [[clang::noinline]] own = prm_env(k ? m.prm_bias : m.prm_gain, scr, m.S.xfrc, 3 * m.nu, 3 * a + 2, own);
+  }
+  return own;
+}
+__device__ __forceinline__ float dof_damping(const DevModel& m, const gfloat* scr, int j, float own) {
+  if (kPrm && (m.prm_mask & kPrmDamp)) { [[clang::noinline]] own = prm_env(m.prm_damp, scr, m.S.xfrc, m.nv, j, own); }
+  return own;
+}
+
 // mj_xfrcAccumulate (batches that use xfrc_applied only): the joint-space force of the per-body
 // Cartesian wrenches on lane's dof j, sum over the bodies b of j's subtree (the others' Jacobian
 // columns are zero) of J_b(xipos_b)' f_b + axis_j' tau_b -- the translational column from jac_col, the
@@ -2776,6 +2841,17 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS) {
       if (m.na > 0) { [[clang::noinline]] ctrl = act_input<G>(ENV_ARGS, a, ctrl); }
       float gain = __float_as_int(ar[6]) == MRS_GAIN_AFFINE ? ar[7] + ar[8] * len + ar[9] * vel : ar[7];
       float bias = __float_as_int(ar[10]) == MRS_BIAS_AFFINE ? ar[11] + ar[12] * len + ar[13] * vel : 0.0f;
+      // per-env gainprm / biasprm (batches that set them only; the types stay the model's)
+      if (kPrm && (m.prm_mask & kPrmGain)) {
+        if (__float_as_int(ar[6]) == MRS_GAIN_AFFINE) {
+          [[clang::noinline]] gain = act_affine_env(m.prm_gain, scr, S.xfrc, m.nu, a, ar[7], ar[8], ar[9], len, vel);
+        } else {  // a fixed gain: gainprm[0] alone
+          [[clang::noinline]] gain = prm_env(m.prm_gain, scr, S.xfrc, 3 * m.nu, 3 * a, ar[7]);
+        }
+      }
+      if (kPrm && (m.prm_mask & kPrmBias) && __float_as_int(ar[10]) == MRS_BIAS_AFFINE) {  // (bias none: no biasprm)
+        [[clang::noinline]] bias = act_affine_env(m.prm_bias, scr, S.xfrc, m.nu, a, ar[11], ar[12], ar[13], len, vel);
+      }
       force = gain * ctrl + bias;
       if (__float_as_int(ar[14])) force = clampf(force, ar[15], ar[16]);
     }
@@ -2811,7 +2887,7 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS) {
         const int qadr = __float_as_int(dr[7]);
         pas -= dr[6] * (s[L.qpos + qadr] - dr[8]);
       }
-      pas -= dr[9] * s[L.qvel + j];
+      pas -= dof_damping(m, scr, j, dr[9]) * s[L.qvel + j];
       // tendon springs (dead band [lengthspring0, lengthspring1]) and dampers through J'
       #pragma unroll 1
       for (int t = 0; t < m.ntendon; ++t) {
@@ -3906,7 +3982,7 @@ __device__ float constraints_sparse(ENV_PARAMS, int ncon, float qacc_s) {
       } else {
         const int p = __float_as_int(scr[S.con + kConRec * id]);
         dim = m.pair_dim[p];
-        mu = m.pair_friction[3 * p];  // sliding, for both tangent directions
+        mu = pair_mu(m, scr, p);  // sliding, for both tangent directions
         sr = m.pair_solref + 2 * p; si = m.pair_solimp + 5 * p;
         const float tran = m.body_invweight0[2 * m.geom_bodyid[m.pair_g1[p]]] + m.body_invweight0[2 * m.geom_bodyid[m.pair_g2[p]]];
         // pyramid edges: diagApprox tran (1 + mu^2), regulariser scaled by 2 mu^2 / impratio
@@ -4808,7 +4884,7 @@ __device__ __forceinline__ bool ell_start(const DevModel& m, const gfloat* type,
 // the block's friction coefficient (both tangents: sliding) and regularised cone mu = mu_1 / sqrt(impratio)
 __device__ __forceinline__ float ell_friction(const DevModel& m, const gfloat* scr, const gfloat* type, int r) {
   const int c = __float_as_int(type[r]) & 0xffff;
-  return m.pair_friction[3 * __float_as_int(scr[m.S.con + kConRec * c])];
+  return pair_mu(m, scr, __float_as_int(scr[m.S.con + kConRec * c]));
 }
 // zone (PST_SAT top, PST_QUAD bottom, PST_CONE middle) at jar; f, cost and the jar-space Hessian H may
 // be null
@@ -5784,7 +5860,7 @@ __device__ __forceinline__ void row_impedance(const DevModel& m, const lfloat* s
     } else if (m.pair_dim[p] == 3) {
       // pyramid edge: diagApprox tran (1 + mu^2) (mu sliding, for both tangent directions);
       // mj_makeImpedance scales the edges' regulariser by 2 mu^2 / impratio
-      const float mu = m.pair_friction[3 * p];
+      const float mu = pair_mu(m, scr, p);
       diag = tran * (1 + mu * mu) * (2 * mu * mu / m.impratio);
     }
   }
@@ -6044,7 +6120,7 @@ __device__ int dense_rows(ENV_PARAMS, int ncon) {
       const int dl = m.pair_dim[pl];
       const int b1l = m.geom_bodyid[m.pair_g1[pl]], b2l = m.geom_bodyid[m.pair_g2[pl]];
       const int r1l = m.body_rootid[b1l], r2l = m.body_rootid[b2l];
-      const float mul = m.pair_friction[3 * pl], mgl = m.pair_margin[pl] - m.pair_gap[pl];
+      const float mul = pair_mu(m, scr, pl), mgl = m.pair_margin[pl] - m.pair_gap[pl];
       const int nc = ncon - c0 < 64 ? ncon - c0 : 64;
       #pragma unroll 1
       for (int k = 0; k < nc; ++k) {
@@ -6130,7 +6206,7 @@ __device__ int dense_rows(ENV_PARAMS, int ncon) {
           if (nefc >= m.max_efc) continue;
           // both tangent directions use the sliding coefficient (contact friction is
           // (slide, slide, spin, roll, roll) from the geoms' (slide, spin, roll), mj_setContact)
-          const float mu = m.pair_friction[3 * p];
+          const float mu = pair_mu(m, scr, p);
           if (lane < nv) J[nefc * nv + lane] = jc[0] + sg * mu * jc[k];
           if (lane == 0) {
             type[nefc] = __int_as_float(EFC_CONTACT * 65536 + c);
@@ -6536,7 +6612,7 @@ __device__ MRS_PHASE void rne_post(ENV_PARAMS, int ncon) {
           for (int k = 0; k < 2; ++k) {
             const float fp = ff[r0 + 2 * k], fm = ff[r0 + 2 * k + 1];
             lf[0] += fp + fm;
-            lf[k + 1] = (fp - fm) * m.pair_friction[3 * p];
+            lf[k + 1] = (fp - fm) * pair_mu(m, scr, p);
           }
         }
         float F[3];
@@ -6906,7 +6982,7 @@ __device__ void rays_chunked(ENV_PARAMS, gfloat* sensordata) {
 
 // the sweep code is left out of the helper-wave kernels' translation unit (they keep the block passes;
 // batch.hip never sets rf_sweep with helper waves)
-#if defined(MRS_STEP_PART) && MRS_STEP_PART == 19
+#if defined(MRS_STEP_PART) && (MRS_STEP_PART == 19 || MRS_STEP_PART == 120)
 constexpr bool kRaySweepBuilt = false;
 #else
 constexpr bool kRaySweepBuilt = true;
@@ -7583,7 +7659,7 @@ __device__ __forceinline__ float integrate_dg(ENV_PARAMS) {
   float dg = 0;
   if (lane < nv) {
     const auto dr = dof_tab<G>(m, lane);
-    const float damping = dr[9];
+    const float damping = dof_damping(m, scr, lane, dr[9]);
     if (m.integrator == MRS_INT_EULER) {
       if (!(m.disableflags & MRS_DSBL_EULERDAMP) && damping > 0) dg = damping;
     } else {
@@ -7597,8 +7673,8 @@ __device__ __forceinline__ float integrate_dg(ENV_PARAMS) {
             const float f = s[L.act_force + a];
             if (f <= ar[15] || f >= ar[16]) return;
           }
-          const float bv = __float_as_int(ar[10]) == MRS_BIAS_AFFINE ? ar[13] : 0.0f;
-          const float gv = __float_as_int(ar[6]) == MRS_GAIN_AFFINE ? ar[9] : 0.0f;
+          const float bv = __float_as_int(ar[10]) == MRS_BIAS_AFFINE ? act_vel_coef(m, scr, a, 1, ar[13]) : 0.0f;
+          const float gv = __float_as_int(ar[6]) == MRS_GAIN_AFFINE ? act_vel_coef(m, scr, a, 0, ar[9]) : 0.0f;
           float ctrl = s[L.ctrl + a];
           if (__float_as_int(ar[3]) && !(m.disableflags & MRS_DSBL_CLAMPCTRL)) ctrl = clampf(ctrl, ar[4], ar[5]);
           if (m.na > 0) { [[clang::noinline]] ctrl = act_state<G>(ENV_ARGS, a, ctrl); }
@@ -7691,10 +7767,11 @@ __device__ MRS_PHASE void integrate(ENV_PARAMS, bool prefac = false) {
 // the velocity derivative of the actuators and passive forces on lane j's dof, as integrate()'s
 // implicitfast path (minus the derivative of qfrc_passive + qfrc_actuator)
 template <int G>
-__device__ __forceinline__ float implicit_dg(const DevModel* mp, const DevModel& m, const lfloat* s, int lane) {
+__device__ __forceinline__ float implicit_dg(const DevModel* mp, const DevModel& m, const lfloat* s, const gfloat* scr,
+                                             int lane) {
   const LdsLayout& L = m.L;
   const auto dr = dof_tab<G>(m, lane);
-  float dg = (m.disableflags & MRS_DSBL_PASSIVE) ? 0.0f : dr[9];
+  float dg = (m.disableflags & MRS_DSBL_PASSIVE) ? 0.0f : dof_damping(m, scr, lane, dr[9]);
   if (!(m.disableflags & MRS_DSBL_ACTUATION)) {
     auto act_dv = [&](int a) {
       const auto ar = act_tab<G>(m, a);
@@ -7702,8 +7779,8 @@ __device__ __forceinline__ float implicit_dg(const DevModel* mp, const DevModel&
         const float f = s[L.act_force + a];
         if (f <= ar[15] || f >= ar[16]) return;
       }
-      const float bv = __float_as_int(ar[10]) == MRS_BIAS_AFFINE ? ar[13] : 0.0f;
-      const float gv = __float_as_int(ar[6]) == MRS_GAIN_AFFINE ? ar[9] : 0.0f;
+      const float bv = __float_as_int(ar[10]) == MRS_BIAS_AFFINE ? act_vel_coef(m, scr, a, 1, ar[13]) : 0.0f;
+      const float gv = __float_as_int(ar[6]) == MRS_GAIN_AFFINE ? act_vel_coef(m, scr, a, 0, ar[9]) : 0.0f;
       float ctrl = s[L.ctrl + a];
       if (__float_as_int(ar[3]) && !(m.disableflags & MRS_DSBL_CLAMPCTRL)) ctrl = clampf(ctrl, ar[4], ar[5]);
       if (m.na > 0) { [[clang::noinline]] ctrl = act_state<G>(mp, (lfloat*)s, nullptr, lane, a, ctrl); }
@@ -7739,7 +7816,7 @@ __device__ void integrate_implicit(ENV_PARAMS) {
   const int nv = m.nv;
   const float h = m.timestep;
   const float qacc = lane < nv ? s[L.qacc + lane] : 0.0f;
-  const float dg = lane < nv ? implicit_dg<G>(mp, m, s, lane) : 0.0f;
+  const float dg = lane < nv ? implicit_dg<G>(mp, m, s, scr, lane) : 0.0f;
   const float rhs = lane < nv ? s[L.qfrc_smooth + lane] + s[L.qfrc_con + lane] : 0.0f;
   int ta = 0, tn = nv, tmax = nv;
   if constexpr (G == 64) {
@@ -7939,9 +8016,9 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
       s[L.mocap + i] = c < 3 ? m.mocap_pos[(e * m.nmocap + k) * 3 + c] : m.mocap_quat[(e * m.nmocap + k) * 4 + c - 3];
     }
   }
-  // xfrc_applied in use: the group's row of it for the phases (xfrc_row) -- a mirror group reads its
-  // primary's env, a group past n_envs none
-  if (st.xfrc_applied && lane == 0 && !is_helper) scr[m.S.xfrc] = __int_as_float(env < n_envs ? env : -1);
+  // xfrc_applied or a per-env model parameter in use: the group's row of them for the phases (xfrc_row,
+  // prm_at) -- a mirror group reads its primary's env, a group past n_envs none
+  if ((st.xfrc_applied || (kPrm && m.prm_mask)) && lane == 0 && !is_helper) scr[m.S.xfrc] = __int_as_float(env < n_envs ? env : -1);
   if constexpr (G == 64) {
     #pragma unroll 1
     for (int t = lane; t < m.ntree; t += G) {
@@ -8224,8 +8301,8 @@ int phase_cycles(double* out, int n, bool reset) {
 #ifndef MRS_STEP_PART
 // single translation unit: every instantiation (the variant builds, scripts/build_variant.sh)
 hipError_t launch_step(const DevModel* d_model, int lds_floats, int shared_floats, const DevState& st, int n_envs,
-                       int n_steps, bool forward_only, int group, bool primal, bool ext, hipStream_t stream) {
-  (void)ext;  // (one translation unit: MRS_EXT as compiled)
+                       int n_steps, bool forward_only, int group, bool primal, bool ext, bool params, hipStream_t stream) {
+  (void)ext; (void)params;  // (one translation unit: MRS_EXT and MRS_PRM as compiled)
   switch (group) {
     case 8: launch_g<8>(d_model, lds_floats, shared_floats, st, n_envs, n_steps, forward_only, primal, stream); break;
     case 16: launch_g<16>(d_model, lds_floats, shared_floats, st, n_envs, n_steps, forward_only, primal, stream); break;
@@ -8253,9 +8330,29 @@ void launch_part_19(MRS_LAUNCH_ARGS);
 void launch_part_32(MRS_LAUNCH_ARGS);
 void launch_part_64(MRS_LAUNCH_ARGS);
 void launch_part_65(MRS_LAUNCH_ARGS);
+// the kernels with the per-env model parameter reads (MRS_PRM 1; 120 without, the others with the
+// extended code): G = 8, G = 16, G = 16 with helper waves, G = 32, G = 64
+void launch_part_108(MRS_LAUNCH_ARGS);
+void launch_part_116(MRS_LAUNCH_ARGS);
+void launch_part_120(MRS_LAUNCH_ARGS);
+void launch_part_132(MRS_LAUNCH_ARGS);
+void launch_part_164(MRS_LAUNCH_ARGS);
 #if MRS_STEP_PART == 0
 hipError_t launch_step(const DevModel* d_model, int lds_floats, int shared_floats, const DevState& st, int n_envs,
-                       int n_steps, bool forward_only, int group, bool primal, bool ext, hipStream_t stream) {
+                       int n_steps, bool forward_only, int group, bool primal, bool ext, bool params, hipStream_t stream) {
+  if (params) {  // a per-env model parameter is in use (DevModel::prm_mask != 0)
+    switch (group) {
+      case 8: launch_part_108(MRS_LAUNCH_PASS); break;
+      case 16:
+        if (st.ray_helpers && !forward_only) launch_part_120(MRS_LAUNCH_PASS);
+        else launch_part_116(MRS_LAUNCH_PASS);
+        break;
+      case 32: launch_part_132(MRS_LAUNCH_PASS); break;
+      case 64: launch_part_164(MRS_LAUNCH_PASS); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   switch (group) {
     case 8: launch_part_8(MRS_LAUNCH_PASS); break;
     case 16:
@@ -8284,6 +8381,16 @@ void launch_part_18(MRS_LAUNCH_ARGS) { launch_g<16, kSelForward | kSelStep | kSe
 void launch_part_19(MRS_LAUNCH_ARGS) { launch_g<16, kSelHelpers>(MRS_LAUNCH_PASS); }
 #elif MRS_STEP_PART == 65
 void launch_part_65(MRS_LAUNCH_ARGS) { launch_g<64>(MRS_LAUNCH_PASS); }
+#elif MRS_STEP_PART == 108
+void launch_part_108(MRS_LAUNCH_ARGS) { launch_g<8>(MRS_LAUNCH_PASS); }
+#elif MRS_STEP_PART == 116
+void launch_part_116(MRS_LAUNCH_ARGS) { launch_g<16, kSelForward | kSelStep | kSelPrimal>(MRS_LAUNCH_PASS); }
+#elif MRS_STEP_PART == 120
+void launch_part_120(MRS_LAUNCH_ARGS) { launch_g<16, kSelHelpers>(MRS_LAUNCH_PASS); }
+#elif MRS_STEP_PART == 132
+void launch_part_132(MRS_LAUNCH_ARGS) { launch_g<32>(MRS_LAUNCH_PASS); }
+#elif MRS_STEP_PART == 164
+void launch_part_164(MRS_LAUNCH_ARGS) { launch_g<64>(MRS_LAUNCH_PASS); }
 #else
 #define MRS_PART_FN2(n) launch_part_##n
 #define MRS_PART_FN(n) MRS_PART_FN2(n)

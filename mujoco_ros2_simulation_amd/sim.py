@@ -36,6 +36,8 @@ RESTATE_NEWTON_REFINE, RESTATE_PGS_ELLIPTIC_BLOCK, RESTATE_NO_MPR_POLISH, RESTAT
 (FIELD_QPOS, FIELD_QVEL, FIELD_CTRL, FIELD_QFRC_APPLIED, FIELD_QACC_WARMSTART, FIELD_QACC,
  FIELD_QFRC_ACTUATOR, FIELD_SENSORDATA, FIELD_TIME, FIELD_WARNING, FIELD_NCON, FIELD_SOLVER_NITER,
  FIELD_XFRC_APPLIED) = range(13)
+# per-env model parameters (MRS_PARAM_*; Batch.get_model_param / set_model_param)
+PARAM_ACT_GAINPRM, PARAM_ACT_BIASPRM, PARAM_DOF_DAMPING, PARAM_GEOM_FRICTION = range(4)
 # ActuatorType (include/mujoco_ros2_control/data.hpp:43-51 numbering)
 ACT_UNKNOWN, ACT_MOTOR, ACT_POSITION, ACT_VELOCITY, ACT_CUSTOM = range(5)
 
@@ -240,6 +242,11 @@ def lib() -> C.CDLL:
         L.mrs_batch_mocap_pos_device_ptr.argtypes = [C.c_void_p]
         L.mrs_batch_mocap_quat_device_ptr.restype = C.c_void_p
         L.mrs_batch_mocap_quat_device_ptr.argtypes = [C.c_void_p]
+        L.mrs_batch_param_dim.argtypes = [C.c_void_p, C.c_int]
+        L.mrs_batch_set_param.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        L.mrs_batch_get_param.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        L.mrs_batch_param_device_ptr.restype = C.c_void_p
+        L.mrs_batch_param_device_ptr.argtypes = [C.c_void_p, C.c_int]
         L.mrs_batch_set_ctrl_device.argtypes = [C.c_void_p, C.c_void_p]
         L.mrs_batch_bind_ctrl_device.argtypes = [C.c_void_p, C.c_void_p]
         L.mrs_batch_set_timing.argtypes = [C.c_void_p, C.c_int]
@@ -456,6 +463,40 @@ class Batch:
     def mocap_quat_device_ptr(self) -> int:
         """mocap_quat on the device, fp32 [n, nmocap, 4] (0 when nmocap == 0)"""
         return lib().mrs_batch_mocap_quat_device_ptr(self._h) or 0
+
+    def _param_shape(self, param: int) -> tuple:
+        dim = lib().mrs_batch_param_dim(self._h, param)
+        if dim < 0:
+            raise MrsError(dim, lib().mrs_last_error().decode())
+        return (dim // 3, 3) if param in (PARAM_ACT_GAINPRM, PARAM_ACT_BIASPRM) else (dim,)
+
+    def get_model_param(self, param: int, env0: int = 0, n: int | None = None) -> np.ndarray:
+        """per-env model parameter PARAM_*: actuator gainprm / biasprm [0:3] as [n, nu, 3], dof damping
+        [n, nv], geom sliding friction [n, ngeom]; the model's own values until the parameter is set"""
+        n = self.n - env0 if n is None else n
+        shape = self._param_shape(param)
+        out = np.empty((max(n, 0),) + shape, dtype=np.float64)
+        _check(lib().mrs_batch_get_param(self._h, param, out.ctypes.data, env0, n))
+        return out
+
+    def set_model_param(self, param: int, values, env0: int = 0) -> None:
+        """write a model parameter of envs [env0, env0 + n); one row of values broadcasts over the envs
+        from env0 on.  Takes effect at the next step / forward launch; resets keep it"""
+        shape = self._param_shape(param)
+        if 0 in shape:  # e.g. gainprm of a model without actuators
+            return
+        a = np.asarray(values, dtype=np.float64)
+        if a.ndim == len(shape):
+            a = np.broadcast_to(a, (self.n - env0,) + shape)
+        a = np.ascontiguousarray(a).reshape((-1,) + shape)
+        if a.size == 0:
+            return
+        _check(lib().mrs_batch_set_param(self._h, param, a.ctypes.data, env0, a.shape[0]))
+
+    def model_param_device_ptr(self, param: int) -> int:
+        """the parameter's buffer on the device, fp32 [n_envs, dim], ordered on the batch stream (made on
+        first use; 0 when the model has none of it)"""
+        return lib().mrs_batch_param_device_ptr(self._h, param) or 0
 
     def reset(self, key: int = -1, env0: int = 0, n: int | None = None) -> None:
         _check(lib().mrs_batch_reset(self._h, key, env0, self.n - env0 if n is None else n))
