@@ -38,7 +38,7 @@ float* batch_mocap_pos_device_ptr(BatchImpl* b);   // null when nmocap == 0
 float* batch_mocap_quat_device_ptr(BatchImpl* b);  // null when nmocap == 0
 // per-env model parameters (MRS_PARAM_*): floats per env (throws on a bad param), host rows [n][dim],
 // and the device buffer [n_envs][dim], made on the first set / device_ptr (null when dim == 0)
-int batch_param_dim(const BatchImpl* b, int param);
+int batch_param_dim(BatchImpl* b, int param);
 void batch_set_param(BatchImpl* b, int param, const double* host, int env0, int n);
 void batch_get_param(BatchImpl* b, int param, double* host, int env0, int n);
 float* batch_param_device_ptr(BatchImpl* b, int param);

@@ -9,9 +9,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <functional>
+#include <initializer_list>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../../include/mrs.h"
@@ -20,6 +24,7 @@
 #include "devmodel.h"
 #include "raymesh.h"
 #include "lit.h"
+#include "start_rows.h"
 
 namespace mrs {
 
@@ -973,9 +978,10 @@ struct BatchImpl {
   // a caller's device buffer [n][nu] the step launches read ctrl from (batch_bind_ctrl_device; null:
   // st.ctrl, the batch's own buffer)
   const float* ctrl_bound = nullptr;
-  // start states of the masked reset (reset_masked_kernel), fp32 in the state fields' layout: the
-  // model's table [1 + nkey] (row 0 qpos0 with zero qvel / ctrl / time, row 1 + k keyframe k; made at
-  // batch creation) and the runtime pool [pool_n] of batch_set_start_states (capacity pool_cap rows)
+  // the model's start states (start_rows.h): batch_reset copies a row of them from here, and tab_* is
+  // their upload, which the masked reset (reset_masked_kernel) reads, next to the runtime pool [pool_n]
+  // of batch_set_start_states (capacity pool_cap rows)
+  StartRows start;
   float *tab_qpos = nullptr, *tab_qvel = nullptr, *tab_ctrl = nullptr, *tab_act = nullptr;
   float *tab_mpos = nullptr, *tab_mquat = nullptr;  // the mocap poses' rows (row 0: the bodies' pos / quat)
   double* tab_time = nullptr;
@@ -2283,29 +2289,149 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
   S.sens = take(std::max(1, m.nsensordata));
   S.xfrc = take(1);
   S.total = off;
-  // the mocap poses (batch_reset fills them)
-  d.mocap_pos = m.nmocap > 0 ? static_cast<float*>(dalloc(b, static_cast<size_t>(b.n) * 3 * m.nmocap * sizeof(float))) : nullptr;
-  d.mocap_quat = m.nmocap > 0 ? static_cast<float*>(dalloc(b, static_cast<size_t>(b.n) * 4 * m.nmocap * sizeof(float))) : nullptr;
   b.d_dm = static_cast<DevModel*>(dalloc(b, sizeof(DevModel)));
   HIP_CHECK(hipMemcpyAsync(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice, b.stream));
   HIP_CHECK(hipStreamSynchronize(b.stream));
 }
 
-int field_dim(const Model& m, int field) {
-  switch (field) {
-    case MRS_FIELD_QPOS: return m.nq;
-    case MRS_FIELD_QVEL: case MRS_FIELD_QFRC_APPLIED: case MRS_FIELD_QACC_WARMSTART: case MRS_FIELD_QACC:
-    case MRS_FIELD_QFRC_ACTUATOR: return m.nv;
-    case MRS_FIELD_CTRL: return m.nu;
-    case MRS_FIELD_SENSORDATA: return m.nsensordata;
-    case MRS_FIELD_TIME: return 1;
-    case MRS_FIELD_WARNING: return 4;
-    case MRS_FIELD_NCON: return 1;
-    case MRS_FIELD_SOLVER_NITER: return 1;
-    case MRS_FIELD_XFRC_APPLIED: return 6 * m.nbody;
-  }
-  return -1;
+// ---- the per-env arrays: every array [n_envs][dim] that the host reads or writes by env range.  One
+// row of env_array() describes one array -- where the kernels read its pointer (a member of DevState or
+// DevModel: the table points at that slot and keeps no copy), its elements per env, their type and
+// when the array is made -- and creation, the row copies and the accessors below all go by it.
+// Ids: the MRS_FIELD_* values, then
+enum { kArrAct = MRS_FIELD_COUNT, kArrMocapPos, kArrMocapQuat, kArrParam0, kArrCount = kArrParam0 + MRS_PARAM_COUNT };
+
+struct EnvArray {
+  enum Type { F32, I32, F64 } type;
+  // AT_CREATE: with the batch, a buffer even when dim == 0; IF_DIM: with the batch, null when dim == 0;
+  // ON_USE: null until first used (ensure_xfrc, ensure_param)
+  enum Made { AT_CREATE, IF_DIM, ON_USE } made;
+  int dim;     // elements per env; -1: no such array
+  void* ptr;   // the array as its slot holds it now (null: not made)
+  void* slot;  // the pointer member itself
+  size_t width() const { return type == F64 ? sizeof(double) : 4; }
+  // (the slots are float*, const float*, int* and double* members: written as the pointer's bytes)
+  void bind(void* p) const { std::memcpy(slot, &p, sizeof p); }
+};
+
+template <class T>
+EnvArray env_array_at(T*& slot, int dim, EnvArray::Made made = EnvArray::AT_CREATE) {
+  using U = typename std::remove_const<T>::type;
+  return {std::is_same<U, double>::value ? EnvArray::F64 : std::is_same<U, int>::value ? EnvArray::I32 : EnvArray::F32,
+          made, dim, const_cast<U*>(slot), &slot};
 }
+
+EnvArray env_array(BatchImpl& b, int id) {
+  const Model& m = *b.model;
+  DevState& s = b.st;
+  DevModel& d = b.dm;
+  switch (id) {
+    case MRS_FIELD_QPOS: return env_array_at(s.qpos, m.nq);
+    case MRS_FIELD_QVEL: return env_array_at(s.qvel, m.nv);
+    case MRS_FIELD_CTRL: return env_array_at(s.ctrl, m.nu);
+    case MRS_FIELD_QFRC_APPLIED: return env_array_at(s.qfrc_applied, m.nv);
+    case MRS_FIELD_QACC_WARMSTART: return env_array_at(s.qacc_ws, m.nv);
+    case MRS_FIELD_QACC: return env_array_at(s.qacc, m.nv);
+    case MRS_FIELD_QFRC_ACTUATOR: return env_array_at(s.qfrc_act, m.nv);
+    case MRS_FIELD_SENSORDATA: return env_array_at(s.sensordata, m.nsensordata);
+    case MRS_FIELD_TIME: return env_array_at(s.time, 1);
+    case MRS_FIELD_WARNING: return env_array_at(s.warning, 4);
+    case MRS_FIELD_NCON: return env_array_at(s.ncon, 1);
+    case MRS_FIELD_SOLVER_NITER: return env_array_at(s.niter, 1);
+    case MRS_FIELD_XFRC_APPLIED: return env_array_at(s.xfrc_applied, 6 * m.nbody, EnvArray::ON_USE);
+    case kArrAct: return env_array_at(s.act, m.na, EnvArray::IF_DIM);
+    case kArrMocapPos: return env_array_at(d.mocap_pos, 3 * m.nmocap, EnvArray::IF_DIM);
+    case kArrMocapQuat: return env_array_at(d.mocap_quat, 4 * m.nmocap, EnvArray::IF_DIM);
+    case kArrParam0 + MRS_PARAM_ACT_GAINPRM: return env_array_at(d.prm_gain, 3 * m.nu, EnvArray::ON_USE);
+    case kArrParam0 + MRS_PARAM_ACT_BIASPRM: return env_array_at(d.prm_bias, 3 * m.nu, EnvArray::ON_USE);
+    case kArrParam0 + MRS_PARAM_DOF_DAMPING: return env_array_at(d.prm_damp, m.nv, EnvArray::ON_USE);
+    case kArrParam0 + MRS_PARAM_GEOM_FRICTION: return env_array_at(d.prm_fric, m.ngeom, EnvArray::ON_USE);
+  }
+  return {EnvArray::F32, EnvArray::ON_USE, -1, nullptr, nullptr};
+}
+EnvArray field_array(BatchImpl& b, int field) {
+  if (field < 0 || field >= MRS_FIELD_COUNT) throw std::invalid_argument("unknown field");
+  return env_array(b, field);
+}
+EnvArray param_array(BatchImpl& b, int param) {
+  if (param < 0 || param >= MRS_PARAM_COUNT) throw std::invalid_argument("unknown model parameter");
+  return env_array(b, kArrParam0 + param);
+}
+void check_env_range(const BatchImpl& b, int env0, int n) {
+  if (env0 < 0 || n < 0 || env0 + n > b.n) throw std::invalid_argument("env range out of bounds");
+}
+
+// the arrays made with the batch, zero-filled.  Called before build_devmodel: the mocap poses' pointers
+// travel in the model block it uploads
+void make_env_arrays(BatchImpl& b) {
+  for (int id = 0; id < kArrCount; ++id) {
+    const EnvArray a = env_array(b, id);
+    if (a.made == EnvArray::ON_USE || (a.made == EnvArray::IF_DIM && a.dim == 0)) continue;
+    a.bind(dalloc(b, static_cast<size_t>(b.n) * std::max(1, a.dim) * a.width()));
+  }
+}
+
+// ---- the two row copies every host accessor goes through.  Each part is an array and the host's fp64
+// rows [n][dim] for envs [env0, env0 + n); a part with a null host pointer or no elements is skipped.
+// Every part's copy is queued on the batch stream, then the stream is synchronised once (not at all if
+// nothing was queued).  The caller has checked the env range and made the arrays
+struct RowStage { double* host; std::vector<float> f; std::vector<int> i; };
+
+// fp64 host rows into the arrays: static_cast to float (F32) or int (I32), as they are (F64)
+void rows_to_device(BatchImpl& b, int env0, int n, std::initializer_list<std::pair<EnvArray, const double*>> parts) {
+  HIP_CHECK(hipSetDevice(b.device));
+  std::deque<RowStage> stage;  // the converted rows, alive until the synchronise
+  bool queued = false;
+  for (const auto& part : parts) {
+    const EnvArray& a = part.first;
+    const double* host = part.second;
+    const size_t cnt = static_cast<size_t>(n) * std::max(0, a.dim);
+    if (!host || cnt == 0) continue;
+    const void* src = host;
+    if (a.type == EnvArray::F32) {
+      std::vector<float>& t = stage.emplace_back().f;
+      t.resize(cnt);
+      for (size_t k = 0; k < cnt; ++k) t[k] = static_cast<float>(host[k]);
+      src = t.data();
+    } else if (a.type == EnvArray::I32) {
+      std::vector<int>& t = stage.emplace_back().i;
+      t.resize(cnt);
+      for (size_t k = 0; k < cnt; ++k) t[k] = static_cast<int>(host[k]);
+      src = t.data();
+    }
+    HIP_CHECK(hipMemcpyAsync(static_cast<char*>(a.ptr) + static_cast<size_t>(env0) * a.dim * a.width(), src,
+                             cnt * a.width(), hipMemcpyHostToDevice, b.stream));
+    queued = true;
+  }
+  if (queued) HIP_CHECK(hipStreamSynchronize(b.stream));
+}
+
+// the arrays' rows into fp64 host rows
+void rows_to_host(BatchImpl& b, int env0, int n, std::initializer_list<std::pair<EnvArray, double*>> parts) {
+  HIP_CHECK(hipSetDevice(b.device));
+  std::deque<RowStage> stage;  // the fp32 / int32 rows, widened after the synchronise
+  bool queued = false;
+  for (const auto& part : parts) {
+    const EnvArray& a = part.first;
+    const size_t cnt = static_cast<size_t>(n) * std::max(0, a.dim);
+    if (!part.second || cnt == 0) continue;
+    void* dst = part.second;
+    if (a.type != EnvArray::F64) {
+      RowStage& t = stage.emplace_back();
+      t.host = part.second;
+      if (a.type == EnvArray::F32) { t.f.resize(cnt); dst = t.f.data(); } else { t.i.resize(cnt); dst = t.i.data(); }
+    }
+    HIP_CHECK(hipMemcpyAsync(dst, static_cast<const char*>(a.ptr) + static_cast<size_t>(env0) * a.dim * a.width(),
+                             cnt * a.width(), hipMemcpyDeviceToHost, b.stream));
+    queued = true;
+  }
+  if (queued) HIP_CHECK(hipStreamSynchronize(b.stream));
+  for (const RowStage& t : stage) {
+    std::copy(t.f.begin(), t.f.end(), t.host);
+    std::copy(t.i.begin(), t.i.end(), t.host);
+  }
+}
+
 // the per-body wrench buffer [n][nbody][6], made and zero-filled when the field is first used; from
 // then on the step kernel reads it (DevState::xfrc_applied, and DevModel::xfrc for the phases).  The
 // earlier launches have finished before the model block changes
@@ -2320,120 +2446,41 @@ float* ensure_xfrc(BatchImpl& b) {
   }
   return b.st.xfrc_applied;
 }
-// per-env model parameters (MRS_PARAM_*): floats per env, -1 for an unknown parameter
-int param_dim(const Model& m, int param) {
-  switch (param) {
-    case MRS_PARAM_ACT_GAINPRM: case MRS_PARAM_ACT_BIASPRM: return 3 * m.nu;
-    case MRS_PARAM_DOF_DAMPING: return m.nv;
-    case MRS_PARAM_GEOM_FRICTION: return m.ngeom;
-  }
-  return -1;
-}
-// the model's own row of a parameter, in the fp32 rounding the kernel's tables hold (actrec, dofrec,
-// pair_friction)
-std::vector<float> param_model_row(const Model& m, int param) {
-  std::vector<float> r(static_cast<size_t>(std::max(0, param_dim(m, param))));
-  for (size_t i = 0; i < r.size(); ++i) {
-    switch (param) {
-      case MRS_PARAM_ACT_GAINPRM: r[i] = static_cast<float>(m.actuator_gainprm[MRS_NGAIN * (i / 3) + i % 3]); break;
-      case MRS_PARAM_ACT_BIASPRM: r[i] = static_cast<float>(m.actuator_biasprm[MRS_NBIAS * (i / 3) + i % 3]); break;
-      case MRS_PARAM_DOF_DAMPING: r[i] = static_cast<float>(m.dof_damping[i]); break;
-      case MRS_PARAM_GEOM_FRICTION: r[i] = static_cast<float>(m.geom_friction[3 * i]); break;
-    }
-  }
-  return r;
-}
-const float*& param_slot(BatchImpl& b, int param) {
-  switch (param) {
-    case MRS_PARAM_ACT_GAINPRM: return b.dm.prm_gain;
-    case MRS_PARAM_ACT_BIASPRM: return b.dm.prm_bias;
-    case MRS_PARAM_DOF_DAMPING: return b.dm.prm_damp;
-    default: return b.dm.prm_fric;
-  }
-}
 // a parameter's buffer [n][dim], made when the parameter is first used and filled with the model's own
 // values for every env; from then on the step kernel reads it (DevModel::prm_*).  Like ensure_xfrc:
 // the earlier launches have finished before the model block changes.  Null when dim == 0
 float* ensure_param(BatchImpl& b, int param) {
-  const int dim = param_dim(*b.model, param);
-  if (dim < 0) throw std::invalid_argument("unknown model parameter");
-  if (dim == 0) return nullptr;
-  const float*& slot = param_slot(b, param);
-  if (!slot) {
-    HIP_CHECK(hipSetDevice(b.device));
-    const std::vector<float> row = param_model_row(*b.model, param);
-    std::vector<float> all(static_cast<size_t>(b.n) * dim);
-    for (int e = 0; e < b.n; ++e) std::copy(row.begin(), row.end(), all.begin() + static_cast<size_t>(e) * dim);
-    float* p = static_cast<float*>(dalloc(b, all.size() * sizeof(float)));
-    HIP_CHECK(hipStreamSynchronize(b.stream));
-    HIP_CHECK(hipMemcpy(p, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
-    slot = p;
-    b.dm.prm_mask |= 1 << param;
-    HIP_CHECK(hipMemcpy(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice));
-  }
-  return const_cast<float*>(slot);
-}
-void* field_ptr(BatchImpl& b, int field) {
-  switch (field) {
-    case MRS_FIELD_QPOS: return b.st.qpos;
-    case MRS_FIELD_QVEL: return b.st.qvel;
-    case MRS_FIELD_CTRL: return b.st.ctrl;
-    case MRS_FIELD_QFRC_APPLIED: return b.st.qfrc_applied;
-    case MRS_FIELD_QACC_WARMSTART: return b.st.qacc_ws;
-    case MRS_FIELD_QACC: return b.st.qacc;
-    case MRS_FIELD_QFRC_ACTUATOR: return b.st.qfrc_act;
-    case MRS_FIELD_SENSORDATA: return b.st.sensordata;
-    case MRS_FIELD_TIME: return b.st.time;
-    case MRS_FIELD_WARNING: return b.st.warning;
-    case MRS_FIELD_NCON: return b.st.ncon;
-    case MRS_FIELD_SOLVER_NITER: return b.st.niter;
-    case MRS_FIELD_XFRC_APPLIED: return ensure_xfrc(b);
-  }
-  return nullptr;
+  const EnvArray a = param_array(b, param);
+  if (a.dim == 0 || a.ptr) return static_cast<float*>(a.ptr);
+  HIP_CHECK(hipSetDevice(b.device));
+  const std::vector<float> row = param_model_row(*b.model, param);
+  std::vector<float> all(static_cast<size_t>(b.n) * a.dim);
+  for (int e = 0; e < b.n; ++e) std::copy(row.begin(), row.end(), all.begin() + static_cast<size_t>(e) * a.dim);
+  float* p = static_cast<float*>(dalloc(b, all.size() * sizeof(float)));
+  HIP_CHECK(hipStreamSynchronize(b.stream));
+  HIP_CHECK(hipMemcpy(p, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
+  a.bind(p);
+  b.dm.prm_mask |= 1 << param;
+  HIP_CHECK(hipMemcpy(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice));
+  return p;
 }
 
-// the model's start states as the masked reset reads them: qpos0 and the keyframes in one device
-// table, converted to fp32 exactly as batch_reset's rows are (key_time stays fp64, like the time field)
+// the model's start states as the masked reset reads them: b.start (start_rows.h) in one device table
 void upload_start_table(BatchImpl& b) {
-  const Model& m = *b.model;
-  const size_t rows = static_cast<size_t>(m.nkey) + 1;
-  std::vector<float> q(rows * m.nq), v(rows * m.nv, 0.0f), c(rows * m.nu, 0.0f), a(rows * m.na, 0.0f);
-  std::vector<float> mp(rows * 3 * m.nmocap), mq(rows * 4 * m.nmocap);
-  std::vector<double> t(rows, 0.0);
-  for (int i = 0; i < m.nq; ++i) q[i] = static_cast<float>(m.qpos0[i]);
-  for (int bd = 0; bd < m.nbody; ++bd) {
-    const int id = m.body_mocapid[bd];
-    if (id < 0) continue;
-    for (int i = 0; i < 3; ++i) mp[3 * id + i] = static_cast<float>(m.body_pos[3 * bd + i]);
-    for (int i = 0; i < 4; ++i) mq[4 * id + i] = static_cast<float>(m.body_quat[4 * bd + i]);
-  }
-  for (int k = 0; k < m.nkey; ++k) {
-    const size_t r = static_cast<size_t>(k) + 1, s = static_cast<size_t>(k);
-    for (int i = 0; i < m.nq; ++i) q[r * m.nq + i] = static_cast<float>(m.key_qpos[s * m.nq + i]);
-    for (int i = 0; i < m.nv; ++i) v[r * m.nv + i] = static_cast<float>(m.key_qvel[s * m.nv + i]);
-    for (int i = 0; i < m.nu; ++i) c[r * m.nu + i] = static_cast<float>(m.key_ctrl[s * m.nu + i]);
-    for (int i = 0; i < m.na; ++i) a[r * m.na + i] = static_cast<float>(m.key_act[s * m.na + i]);
-    for (int i = 0; i < 3 * m.nmocap; ++i) mp[r * 3 * m.nmocap + i] = static_cast<float>(m.key_mpos[s * 3 * m.nmocap + i]);
-    for (int i = 0; i < 4 * m.nmocap; ++i) mq[r * 4 * m.nmocap + i] = static_cast<float>(m.key_mquat[s * 4 * m.nmocap + i]);
-    t[r] = m.key_time[k];
-  }
-  b.tab_qpos = static_cast<float*>(dalloc(b, q.size() * sizeof(float)));
-  b.tab_qvel = static_cast<float*>(dalloc(b, v.size() * sizeof(float)));
-  b.tab_ctrl = static_cast<float*>(dalloc(b, c.size() * sizeof(float)));
-  b.tab_act = static_cast<float*>(dalloc(b, a.size() * sizeof(float)));
-  b.tab_mpos = static_cast<float*>(dalloc(b, mp.size() * sizeof(float)));
-  b.tab_mquat = static_cast<float*>(dalloc(b, mq.size() * sizeof(float)));
-  b.tab_time = static_cast<double*>(dalloc(b, t.size() * sizeof(double)));
-  auto put = [&](void* dst, const void* src, size_t bytes) {
+  auto put = [&](const void* src, size_t bytes) {
+    void* dst = dalloc(b, bytes);
     if (bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, b.stream));
+    return dst;
   };
-  put(b.tab_qpos, q.data(), q.size() * sizeof(float));
-  put(b.tab_qvel, v.data(), v.size() * sizeof(float));
-  put(b.tab_ctrl, c.data(), c.size() * sizeof(float));
-  put(b.tab_act, a.data(), a.size() * sizeof(float));
-  put(b.tab_mpos, mp.data(), mp.size() * sizeof(float));
-  put(b.tab_mquat, mq.data(), mq.size() * sizeof(float));
-  put(b.tab_time, t.data(), t.size() * sizeof(double));
+  auto putf = [&](const std::vector<float>& v) { return static_cast<float*>(put(v.data(), v.size() * sizeof(float))); };
+  const StartRows& s = b.start;
+  b.tab_qpos = putf(s.qpos);
+  b.tab_qvel = putf(s.qvel);
+  b.tab_ctrl = putf(s.ctrl);
+  b.tab_act = putf(s.act);
+  b.tab_mpos = putf(s.mpos);
+  b.tab_mquat = putf(s.mquat);
+  b.tab_time = static_cast<double*>(put(s.time.data(), s.time.size() * sizeof(double)));
   HIP_CHECK(hipStreamSynchronize(b.stream));
 }
 
@@ -2474,22 +2521,11 @@ BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_cont
     HIP_CHECK(hipStreamCreateWithFlags(&b->own_stream, hipStreamNonBlocking));
     b->stream = b->own_stream;
     for (int k = 0; k < 2; ++k) { HIP_CHECK(hipEventCreate(&b->ev0[k])); HIP_CHECK(hipEventCreate(&b->ev1[k])); }
+    b->start = start_rows(*model);
+    make_env_arrays(*b);
     build_devmodel(*b, max_contacts);
     const Model& m = *model;
     const size_t n = static_cast<size_t>(n_envs);
-    b->st.qpos = static_cast<float*>(dalloc(*b, n * std::max(1, m.nq) * sizeof(float)));
-    b->st.qvel = static_cast<float*>(dalloc(*b, n * std::max(1, m.nv) * sizeof(float)));
-    b->st.ctrl = static_cast<float*>(dalloc(*b, n * std::max(1, m.nu) * sizeof(float)));
-    b->st.qfrc_applied = static_cast<float*>(dalloc(*b, n * std::max(1, m.nv) * sizeof(float)));
-    b->st.qacc_ws = static_cast<float*>(dalloc(*b, n * std::max(1, m.nv) * sizeof(float)));
-    b->st.qacc = static_cast<float*>(dalloc(*b, n * std::max(1, m.nv) * sizeof(float)));
-    b->st.qfrc_act = static_cast<float*>(dalloc(*b, n * std::max(1, m.nv) * sizeof(float)));
-    b->st.sensordata = static_cast<float*>(dalloc(*b, n * std::max(1, m.nsensordata) * sizeof(float)));
-    b->st.act = m.na > 0 ? static_cast<float*>(dalloc(*b, n * m.na * sizeof(float))) : nullptr;
-    b->st.time = static_cast<double*>(dalloc(*b, n * sizeof(double)));
-    b->st.warning = static_cast<int*>(dalloc(*b, n * 4 * sizeof(int)));
-    b->st.ncon = static_cast<int*>(dalloc(*b, n * sizeof(int)));
-    b->st.niter = static_cast<int*>(dalloc(*b, n * sizeof(int)));
     // padded to whole workgroups of the chosen group width: idle groups use it
     const size_t epb = static_cast<size_t>(envs_per_block(b->group, b->wpb16));
     const size_t n_pad = (static_cast<size_t>(n) + epb - 1) / epb * epb;
@@ -2573,58 +2609,40 @@ void batch_set_stream(BatchImpl* b, void* stream) {
   b->stream = stream ? static_cast<hipStream_t>(stream) : b->own_stream;
 }
 
+// mj_resetData (key < 0) / mj_resetDataKeyframe of a range of envs by host copy: row key + 1 of the
+// start rows, replicated, through the same row copy as every set.  qacc, qfrc_actuator, sensordata,
+// ncon, solver_niter and the parameters keep their values
 void batch_reset(BatchImpl* b, int key, int env0, int n) {
   const Model& m = *b->model;
-  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
+  check_env_range(*b, env0, n);
   if (key >= m.nkey) throw std::invalid_argument("keyframe index out of range");
+  b->ctrl_bound = nullptr;  // (host ctrl replaces a bound buffer, as in batch_set)
+  if (n == 0) return;
+  const StartRows& s = b->start;
+  const size_t r = key < 0 ? 0 : static_cast<size_t>(key) + 1;
+  auto rows = [&](const std::vector<float>& tab, int dim) {
+    std::vector<double> v(static_cast<size_t>(n) * dim);
+    for (size_t i = 0; i < v.size(); ++i) v[i] = tab[r * dim + i % dim];
+    return v;
+  };
+  const std::vector<double> qpos = rows(s.qpos, m.nq), qvel = rows(s.qvel, m.nv), ctrl = rows(s.ctrl, m.nu),
+                            act = rows(s.act, m.na), mp = rows(s.mpos, 3 * m.nmocap), mq = rows(s.mquat, 4 * m.nmocap),
+                            t(n, s.time[r]), zeros(static_cast<size_t>(n) * std::max(m.nv, 4), 0.0);
   HIP_CHECK(hipSetDevice(b->device));
-  std::vector<double> qpos(static_cast<size_t>(n) * m.nq), qvel(static_cast<size_t>(n) * m.nv, 0.0),
-      ctrl(static_cast<size_t>(n) * m.nu, 0.0), zeros(static_cast<size_t>(n) * m.nv, 0.0), t(n, 0.0);
-  for (int e = 0; e < n; ++e) {
-    const double* q0 = key >= 0 ? &m.key_qpos[static_cast<size_t>(key) * m.nq] : m.qpos0.data();
-    std::copy(q0, q0 + m.nq, &qpos[static_cast<size_t>(e) * m.nq]);
-    if (key >= 0) {
-      std::copy(&m.key_qvel[static_cast<size_t>(key) * m.nv], &m.key_qvel[static_cast<size_t>(key) * m.nv] + m.nv,
-                &qvel[static_cast<size_t>(e) * m.nv]);
-      std::copy(&m.key_ctrl[static_cast<size_t>(key) * m.nu], &m.key_ctrl[static_cast<size_t>(key) * m.nu] + m.nu,
-                &ctrl[static_cast<size_t>(e) * m.nu]);
-      t[e] = m.key_time[key];
-    }
-  }
-  batch_set(b, MRS_FIELD_QPOS, qpos.data(), env0, n);
-  batch_set(b, MRS_FIELD_QVEL, qvel.data(), env0, n);
-  batch_set(b, MRS_FIELD_CTRL, ctrl.data(), env0, n);
-  batch_set(b, MRS_FIELD_QFRC_APPLIED, zeros.data(), env0, n);
-  batch_set(b, MRS_FIELD_QACC_WARMSTART, zeros.data(), env0, n);
-  batch_set(b, MRS_FIELD_TIME, t.data(), env0, n);
-  if (m.na > 0) {  // (mj_resetData zeroes act; mj_resetDataKeyframe copies key_act)
-    std::vector<double> act(static_cast<size_t>(n) * m.na, 0.0);
-    if (key >= 0)
-      for (int e = 0; e < n; ++e)
-        std::copy(&m.key_act[static_cast<size_t>(key) * m.na], &m.key_act[static_cast<size_t>(key) * m.na] + m.na,
-                  &act[static_cast<size_t>(e) * m.na]);
-    batch_set_act(b, act.data(), env0, n);
-  }
-  if (m.nmocap > 0) {  // (mj_resetData: the bodies' pos / quat; mj_resetDataKeyframe: key_mpos / key_mquat)
-    std::vector<double> mp(static_cast<size_t>(n) * 3 * m.nmocap), mq(static_cast<size_t>(n) * 4 * m.nmocap);
-    for (int e = 0; e < n; ++e)
-      for (int bd = 0; bd < m.nbody; ++bd) {
-        const int id = m.body_mocapid[bd];
-        if (id < 0) continue;
-        const double* p = key >= 0 ? &m.key_mpos[(static_cast<size_t>(key) * m.nmocap + id) * 3] : &m.body_pos[3 * bd];
-        const double* q = key >= 0 ? &m.key_mquat[(static_cast<size_t>(key) * m.nmocap + id) * 4] : &m.body_quat[4 * bd];
-        std::copy(p, p + 3, &mp[(static_cast<size_t>(e) * m.nmocap + id) * 3]);
-        std::copy(q, q + 4, &mq[(static_cast<size_t>(e) * m.nmocap + id) * 4]);
-      }
-    batch_set_mocap(b, mp.data(), mq.data(), env0, n);
-  }
-  std::vector<double> w(static_cast<size_t>(n) * 4, 0.0);
-  batch_set(b, MRS_FIELD_WARNING, w.data(), env0, n);
-  if (b->st.xfrc_applied) {  // (mj_resetData zeroes xfrc_applied)
+  if (b->st.xfrc_applied) {  // (mj_resetData zeroes xfrc_applied; a buffer never used stays unmade)
     const size_t row = static_cast<size_t>(6) * m.nbody;
     HIP_CHECK(hipMemsetAsync(b->st.xfrc_applied + env0 * row, 0, n * row * sizeof(float), b->stream));
-    HIP_CHECK(hipStreamSynchronize(b->stream));
   }
+  rows_to_device(*b, env0, n, {{env_array(*b, MRS_FIELD_QPOS), qpos.data()},
+                               {env_array(*b, MRS_FIELD_QVEL), qvel.data()},
+                               {env_array(*b, MRS_FIELD_CTRL), ctrl.data()},
+                               {env_array(*b, MRS_FIELD_QFRC_APPLIED), zeros.data()},
+                               {env_array(*b, MRS_FIELD_QACC_WARMSTART), zeros.data()},
+                               {env_array(*b, MRS_FIELD_TIME), t.data()},
+                               {env_array(*b, kArrAct), act.data()},
+                               {env_array(*b, kArrMocapPos), mp.data()},
+                               {env_array(*b, kArrMocapQuat), mq.data()},
+                               {env_array(*b, MRS_FIELD_WARNING), zeros.data()}});
 }
 
 // ---- start-state pool and masked reset (no reference counterpart: the reference resets one mjData
@@ -2701,180 +2719,82 @@ void batch_reset_masked(BatchImpl* b, const unsigned char* mask, const int* keys
 }
 
 void batch_set(BatchImpl* b, int field, const double* host, int env0, int n) {
-  const Model& m = *b->model;
-  int dim = field_dim(m, field);
-  if (dim < 0) throw std::invalid_argument("unknown field");
-  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
+  EnvArray a = field_array(*b, field);
+  check_env_range(*b, env0, n);
   if (field == MRS_FIELD_CTRL) b->ctrl_bound = nullptr;  // (host ctrl replaces a bound buffer)
-  if (n == 0 || dim == 0) return;
-  HIP_CHECK(hipSetDevice(b->device));
-  const size_t cnt = static_cast<size_t>(n) * dim;
-  char* dst = static_cast<char*>(field_ptr(*b, field));
-  if (field == MRS_FIELD_TIME) {
-    HIP_CHECK(hipMemcpyAsync(dst + sizeof(double) * env0, host, cnt * sizeof(double), hipMemcpyHostToDevice, b->stream));
-  } else if (field == MRS_FIELD_WARNING || field == MRS_FIELD_NCON || field == MRS_FIELD_SOLVER_NITER) {
-    std::vector<int> tmp(cnt);
-    for (size_t i = 0; i < cnt; ++i) tmp[i] = static_cast<int>(host[i]);
-    HIP_CHECK(hipMemcpyAsync(dst + sizeof(int) * static_cast<size_t>(env0) * dim, tmp.data(), cnt * sizeof(int),
-                             hipMemcpyHostToDevice, b->stream));
-    HIP_CHECK(hipStreamSynchronize(b->stream));
-    return;
-  } else {
-    std::vector<float> tmp(cnt);
-    for (size_t i = 0; i < cnt; ++i) tmp[i] = static_cast<float>(host[i]);
-    HIP_CHECK(hipMemcpyAsync(dst + sizeof(float) * static_cast<size_t>(env0) * dim, tmp.data(), cnt * sizeof(float),
-                             hipMemcpyHostToDevice, b->stream));
-    HIP_CHECK(hipStreamSynchronize(b->stream));
-    return;
-  }
-  HIP_CHECK(hipStreamSynchronize(b->stream));
+  if (n == 0 || a.dim == 0) return;
+  if (field == MRS_FIELD_XFRC_APPLIED) a.ptr = ensure_xfrc(*b);
+  rows_to_device(*b, env0, n, {{a, host}});
 }
 
 void batch_get(BatchImpl* b, int field, double* host, int env0, int n) {
-  const Model& m = *b->model;
-  int dim = field_dim(m, field);
-  if (dim < 0) throw std::invalid_argument("unknown field");
-  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
-  if (n == 0 || dim == 0) return;
-  HIP_CHECK(hipSetDevice(b->device));
-  const size_t cnt = static_cast<size_t>(n) * dim;
-  if (field == MRS_FIELD_XFRC_APPLIED && !b->st.xfrc_applied) {  // never used: zeros, and no buffer made
-    std::fill(host, host + cnt, 0.0);
+  EnvArray a = field_array(*b, field);
+  check_env_range(*b, env0, n);
+  if (n == 0 || a.dim == 0) return;
+  if (field == MRS_FIELD_XFRC_APPLIED && !a.ptr) {  // never used: zeros, and no buffer made
+    std::fill(host, host + static_cast<size_t>(n) * a.dim, 0.0);
     return;
   }
-  const char* src = field == MRS_FIELD_CTRL && b->ctrl_bound ? reinterpret_cast<const char*>(b->ctrl_bound)
-                                                               : static_cast<const char*>(field_ptr(*b, field));
-  if (field == MRS_FIELD_TIME) {
-    HIP_CHECK(hipMemcpyAsync(host, src + sizeof(double) * env0, cnt * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    HIP_CHECK(hipStreamSynchronize(b->stream));
-  } else if (field == MRS_FIELD_WARNING || field == MRS_FIELD_NCON || field == MRS_FIELD_SOLVER_NITER) {
-    std::vector<int> tmp(cnt);
-    HIP_CHECK(hipMemcpyAsync(tmp.data(), src + sizeof(int) * static_cast<size_t>(env0) * dim, cnt * sizeof(int),
-                             hipMemcpyDeviceToHost, b->stream));
-    HIP_CHECK(hipStreamSynchronize(b->stream));
-    for (size_t i = 0; i < cnt; ++i) host[i] = tmp[i];
-  } else {
-    std::vector<float> tmp(cnt);
-    HIP_CHECK(hipMemcpyAsync(tmp.data(), src + sizeof(float) * static_cast<size_t>(env0) * dim, cnt * sizeof(float),
-                             hipMemcpyDeviceToHost, b->stream));
-    HIP_CHECK(hipStreamSynchronize(b->stream));
-    for (size_t i = 0; i < cnt; ++i) host[i] = tmp[i];
-  }
+  if (field == MRS_FIELD_CTRL && b->ctrl_bound) a.ptr = const_cast<float*>(b->ctrl_bound);
+  rows_to_host(*b, env0, n, {{a, host}});
 }
 
-void* batch_device_ptr(BatchImpl* b, int field) { return field_ptr(*b, field); }
+void* batch_device_ptr(BatchImpl* b, int field) {
+  return field == MRS_FIELD_XFRC_APPLIED ? ensure_xfrc(*b) : field_array(*b, field).ptr;
+}
 
 void batch_set_act(BatchImpl* b, const double* host, int env0, int n) {
-  const int na = b->model->na;
-  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
-  if (n == 0 || na == 0) return;
-  HIP_CHECK(hipSetDevice(b->device));
-  const size_t cnt = static_cast<size_t>(n) * na;
-  std::vector<float> tmp(cnt);
-  for (size_t i = 0; i < cnt; ++i) tmp[i] = static_cast<float>(host[i]);
-  HIP_CHECK(hipMemcpyAsync(b->st.act + static_cast<size_t>(env0) * na, tmp.data(), cnt * sizeof(float),
-                           hipMemcpyHostToDevice, b->stream));
-  HIP_CHECK(hipStreamSynchronize(b->stream));
+  check_env_range(*b, env0, n);
+  rows_to_device(*b, env0, n, {{env_array(*b, kArrAct), host}});
 }
 
 void batch_get_act(BatchImpl* b, double* host, int env0, int n) {
-  const int na = b->model->na;
-  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
-  if (n == 0 || na == 0) return;
-  HIP_CHECK(hipSetDevice(b->device));
-  const size_t cnt = static_cast<size_t>(n) * na;
-  std::vector<float> tmp(cnt);
-  HIP_CHECK(hipMemcpyAsync(tmp.data(), b->st.act + static_cast<size_t>(env0) * na, cnt * sizeof(float),
-                           hipMemcpyDeviceToHost, b->stream));
-  HIP_CHECK(hipStreamSynchronize(b->stream));
-  for (size_t i = 0; i < cnt; ++i) host[i] = tmp[i];
+  check_env_range(*b, env0, n);
+  rows_to_host(*b, env0, n, {{env_array(*b, kArrAct), host}});
 }
 
 float* batch_act_device_ptr(BatchImpl* b) { return b->st.act; }
 
 void batch_set_mocap(BatchImpl* b, const double* pos, const double* quat, int env0, int n) {
-  const int nm = b->model->nmocap;
-  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
-  if (n == 0 || nm == 0 || (!pos && !quat)) return;
-  HIP_CHECK(hipSetDevice(b->device));
-  std::vector<float> tp, tq;
-  auto put = [&](float* dst, const double* src, int w, std::vector<float>& tmp) {
-    if (!src) return;
-    const size_t cnt = static_cast<size_t>(n) * nm * w;
-    tmp.resize(cnt);
-    for (size_t i = 0; i < cnt; ++i) tmp[i] = static_cast<float>(src[i]);
-    HIP_CHECK(hipMemcpyAsync(dst + static_cast<size_t>(env0) * nm * w, tmp.data(), cnt * sizeof(float),
-                             hipMemcpyHostToDevice, b->stream));
-  };
-  put(b->dm.mocap_pos, pos, 3, tp);
-  put(b->dm.mocap_quat, quat, 4, tq);
-  HIP_CHECK(hipStreamSynchronize(b->stream));
+  check_env_range(*b, env0, n);
+  rows_to_device(*b, env0, n, {{env_array(*b, kArrMocapPos), pos}, {env_array(*b, kArrMocapQuat), quat}});
 }
 
 void batch_get_mocap(BatchImpl* b, double* pos, double* quat, int env0, int n) {
-  const int nm = b->model->nmocap;
-  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
-  if (n == 0 || nm == 0 || (!pos && !quat)) return;
-  HIP_CHECK(hipSetDevice(b->device));
-  std::vector<float> tp(pos ? static_cast<size_t>(n) * nm * 3 : 0), tq(quat ? static_cast<size_t>(n) * nm * 4 : 0);
-  if (pos)
-    HIP_CHECK(hipMemcpyAsync(tp.data(), b->dm.mocap_pos + static_cast<size_t>(env0) * nm * 3, tp.size() * sizeof(float),
-                             hipMemcpyDeviceToHost, b->stream));
-  if (quat)
-    HIP_CHECK(hipMemcpyAsync(tq.data(), b->dm.mocap_quat + static_cast<size_t>(env0) * nm * 4, tq.size() * sizeof(float),
-                             hipMemcpyDeviceToHost, b->stream));
-  HIP_CHECK(hipStreamSynchronize(b->stream));
-  for (size_t i = 0; i < tp.size(); ++i) pos[i] = tp[i];
-  for (size_t i = 0; i < tq.size(); ++i) quat[i] = tq[i];
+  check_env_range(*b, env0, n);
+  rows_to_host(*b, env0, n, {{env_array(*b, kArrMocapPos), pos}, {env_array(*b, kArrMocapQuat), quat}});
 }
 
 float* batch_mocap_pos_device_ptr(BatchImpl* b) { return b->dm.mocap_pos; }
 float* batch_mocap_quat_device_ptr(BatchImpl* b) { return b->dm.mocap_quat; }
 
-int batch_param_dim(const BatchImpl* b, int param) {
-  const int dim = param_dim(*b->model, param);
-  if (dim < 0) throw std::invalid_argument("unknown model parameter");
-  return dim;
-}
+int batch_param_dim(BatchImpl* b, int param) { return param_array(*b, param).dim; }
 
 void batch_set_param(BatchImpl* b, int param, const double* host, int env0, int n) {
-  const int dim = batch_param_dim(b, param);
-  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
-  if (n == 0 || dim == 0) return;
-  const size_t cnt = static_cast<size_t>(n) * dim;
-  // checked before anything is made or written: finite, and no negative damping or friction
+  EnvArray a = param_array(*b, param);
+  check_env_range(*b, env0, n);
+  if (n == 0 || a.dim == 0) return;
+  // checked before anything is made or written: finite (in fp32 too), and no negative damping or friction
   const bool nonneg = param == MRS_PARAM_DOF_DAMPING || param == MRS_PARAM_GEOM_FRICTION;
-  std::vector<float> tmp(cnt);
-  for (size_t i = 0; i < cnt; ++i) {
-    tmp[i] = static_cast<float>(host[i]);
-    if (!std::isfinite(host[i]) || !std::isfinite(tmp[i])) throw std::invalid_argument("model parameter value is not finite");
-    if (nonneg && host[i] < 0) throw std::invalid_argument("negative damping or friction");
+  for (size_t i = 0; i < static_cast<size_t>(n) * a.dim; ++i) {
+    const double x = host[i];
+    if (!std::isfinite(x) || !std::isfinite(static_cast<float>(x))) throw std::invalid_argument("model parameter value is not finite");
+    if (nonneg && x < 0) throw std::invalid_argument("negative damping or friction");
   }
-  HIP_CHECK(hipSetDevice(b->device));
-  float* dst = ensure_param(*b, param);
-  HIP_CHECK(hipMemcpyAsync(dst + static_cast<size_t>(env0) * dim, tmp.data(), cnt * sizeof(float), hipMemcpyHostToDevice,
-                           b->stream));
-  HIP_CHECK(hipStreamSynchronize(b->stream));
+  a.ptr = ensure_param(*b, param);
+  rows_to_device(*b, env0, n, {{a, host}});
 }
 
 void batch_get_param(BatchImpl* b, int param, double* host, int env0, int n) {
-  const int dim = batch_param_dim(b, param);
-  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
-  if (n == 0 || dim == 0) return;
-  const float* src = param_slot(*b, param);
-  if (!src) {  // never used: the model's values for every env, and no buffer made
+  const EnvArray a = param_array(*b, param);
+  check_env_range(*b, env0, n);
+  if (n == 0 || a.dim == 0) return;
+  if (!a.ptr) {  // never used: the model's values for every env, and no buffer made
     const std::vector<float> row = param_model_row(*b->model, param);
-    for (int e = 0; e < n; ++e)
-      for (int i = 0; i < dim; ++i) host[static_cast<size_t>(e) * dim + i] = row[i];
+    for (int e = 0; e < n; ++e) std::copy(row.begin(), row.end(), host + static_cast<size_t>(e) * a.dim);
     return;
   }
-  HIP_CHECK(hipSetDevice(b->device));
-  const size_t cnt = static_cast<size_t>(n) * dim;
-  std::vector<float> tmp(cnt);
-  HIP_CHECK(hipMemcpyAsync(tmp.data(), src + static_cast<size_t>(env0) * dim, cnt * sizeof(float), hipMemcpyDeviceToHost,
-                           b->stream));
-  HIP_CHECK(hipStreamSynchronize(b->stream));
-  for (size_t i = 0; i < cnt; ++i) host[i] = tmp[i];
+  rows_to_host(*b, env0, n, {{a, host}});
 }
 
 float* batch_param_device_ptr(BatchImpl* b, int param) { return ensure_param(*b, param); }
@@ -3120,18 +3040,15 @@ int batch_get_contacts(BatchImpl* b, int env, int max, int* geom, double* dist, 
 // fp32 field rows [env0, env0 + n) into a caller device buffer [n][dim], ordered on the batch stream
 // (observation export without a host round trip, e.g. for the end-of-step RCCL gather)
 void batch_get_field_device(BatchImpl* b, int field, float* d_out, int env0, int n) {
-  const Model& m = *b->model;
-  const int dim = field_dim(m, field);
-  if (dim < 0 || field == MRS_FIELD_TIME || field == MRS_FIELD_WARNING || field == MRS_FIELD_NCON || field == MRS_FIELD_SOLVER_NITER)
-    throw std::invalid_argument("not an fp32 state field");
-  if (env0 < 0 || n < 0 || env0 + n > b->n) throw std::invalid_argument("env range out of bounds");
-  if (n == 0 || dim == 0) return;
+  EnvArray a = env_array(*b, field);
+  if (field < 0 || field >= MRS_FIELD_COUNT || a.type != EnvArray::F32) throw std::invalid_argument("not an fp32 state field");
+  check_env_range(*b, env0, n);
+  if (n == 0 || a.dim == 0) return;
   HIP_CHECK(hipSetDevice(b->device));
-  const float* base = field == MRS_FIELD_CTRL && b->ctrl_bound ? b->ctrl_bound
-                                                               : static_cast<const float*>(field_ptr(*b, field));
-  const float* src = base + static_cast<size_t>(env0) * dim;
-  HIP_CHECK(hipMemcpyAsync(d_out, src, static_cast<size_t>(n) * dim * sizeof(float), hipMemcpyDeviceToDevice,
-                           b->stream));
+  if (field == MRS_FIELD_XFRC_APPLIED) a.ptr = ensure_xfrc(*b);
+  if (field == MRS_FIELD_CTRL && b->ctrl_bound) a.ptr = const_cast<float*>(b->ctrl_bound);
+  HIP_CHECK(hipMemcpyAsync(d_out, static_cast<const float*>(a.ptr) + static_cast<size_t>(env0) * a.dim,
+                           static_cast<size_t>(n) * a.dim * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
 }
 
 void batch_sync(BatchImpl* b) {

@@ -371,10 +371,12 @@ class Model:
             self._h = None
 
 
+# floats per env of a field: a fixed count times a model size (None: 1)
 _FIELD_DIM = {
-    FIELD_QPOS: "nq", FIELD_QVEL: "nv", FIELD_CTRL: "nu", FIELD_QFRC_APPLIED: "nv", FIELD_QACC_WARMSTART: "nv",
-    FIELD_QACC: "nv", FIELD_QFRC_ACTUATOR: "nv", FIELD_SENSORDATA: "nsensordata", FIELD_TIME: 1, FIELD_WARNING: 4,
-    FIELD_NCON: 1, FIELD_SOLVER_NITER: 1, FIELD_XFRC_APPLIED: "6*nbody",
+    FIELD_QPOS: (1, "nq"), FIELD_QVEL: (1, "nv"), FIELD_CTRL: (1, "nu"), FIELD_QFRC_APPLIED: (1, "nv"),
+    FIELD_QACC_WARMSTART: (1, "nv"), FIELD_QACC: (1, "nv"), FIELD_QFRC_ACTUATOR: (1, "nv"),
+    FIELD_SENSORDATA: (1, "nsensordata"), FIELD_TIME: (1, None), FIELD_WARNING: (4, None), FIELD_NCON: (1, None),
+    FIELD_SOLVER_NITER: (1, None), FIELD_XFRC_APPLIED: (6, "nbody"),
 }
 
 
@@ -397,37 +399,43 @@ class Batch:
         self._h = h
 
     def _dim(self, field: int) -> int:
-        d = _FIELD_DIM[field]
-        if field == FIELD_XFRC_APPLIED:
-            return 6 * self.model.nbody
-        return getattr(self.model, d) if isinstance(d, str) else d
+        k, size = _FIELD_DIM[field]
+        return k * getattr(self.model, size) if size else k
+
+    def _get_rows(self, fn, ids: tuple, shapes: list, env0: int, n: int | None, clamp: bool = False) -> list:
+        """fn(handle, *ids, one fp64 out [n, *shape] per shape, env0, n); n None: the envs from env0 on"""
+        n = self.n - env0 if n is None else n
+        outs = [np.empty((max(n, 0) if clamp else n,) + s, dtype=np.float64) for s in shapes]
+        _check(fn(self._h, *ids, *(o.ctypes.data for o in outs), env0, n))
+        return outs
+
+    def _set_rows(self, fn, ids: tuple, shapes: list, values: list, env0: int) -> None:
+        """fn(handle, *ids, one pointer per value as fp64 rows [n, *shape] or None for None, env0, n);
+        a shape without elements (e.g. ctrl of a model without actuators) or only None values: no call"""
+        if any(0 in s for s in shapes) or all(v is None for v in values):
+            return
+        rows = [None if v is None else np.ascontiguousarray(v, dtype=np.float64).reshape((-1,) + s)
+                for v, s in zip(values, shapes)]
+        ns = {r.shape[0] for r in rows if r is not None}
+        if len(ns) > 1:  # (two values: the mocap poses)
+            raise ValueError("pos and quat cover different numbers of envs")
+        _check(fn(self._h, *ids, *(None if r is None else r.ctypes.data for r in rows), env0, ns.pop()))
 
     def get(self, field: int, env0: int = 0, n: int | None = None) -> np.ndarray:
-        n = self.n - env0 if n is None else n
-        out = np.empty((n, self._dim(field)), dtype=np.float64)
-        _check(lib().mrs_batch_get_field(self._h, field, out.ctypes.data, env0, n))
+        out, = self._get_rows(lib().mrs_batch_get_field, (field,), [(self._dim(field),)], env0, n)
         if field == FIELD_XFRC_APPLIED:  # per body: world-frame force, then torque
-            return out.reshape(n, self.model.nbody, 6)
+            return out.reshape(out.shape[0], self.model.nbody, 6)
         return out
 
     def set(self, field: int, values, env0: int = 0) -> None:
-        if self._dim(field) == 0:  # e.g. ctrl of a model without actuators
-            return
-        a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self._dim(field))
-        _check(lib().mrs_batch_set_field(self._h, field, a.ctypes.data, env0, a.shape[0]))
+        self._set_rows(lib().mrs_batch_set_field, (field,), [(self._dim(field),)], [values], env0)
 
     def get_act(self, env0: int = 0, n: int | None = None) -> np.ndarray:
         """mjData.act [n, na]: the activations of the stateful actuators, by actuator_actadr"""
-        n = self.n - env0 if n is None else n
-        out = np.empty((n, self.model.na), dtype=np.float64)
-        _check(lib().mrs_batch_get_act(self._h, out.ctypes.data, env0, n))
-        return out
+        return self._get_rows(lib().mrs_batch_get_act, (), [(self.model.na,)], env0, n)[0]
 
     def set_act(self, values, env0: int = 0) -> None:
-        if self.model.na == 0:
-            return
-        a = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, self.model.na)
-        _check(lib().mrs_batch_set_act(self._h, a.ctypes.data, env0, a.shape[0]))
+        self._set_rows(lib().mrs_batch_set_act, (), [(self.model.na,)], [values], env0)
 
     def act_device_ptr(self) -> int:
         """the activations on the device, fp32 [n, na], ordered on the batch stream (0 when na == 0)"""
@@ -436,25 +444,13 @@ class Batch:
     def get_mocap(self, env0: int = 0, n: int | None = None) -> tuple[np.ndarray, np.ndarray]:
         """mjData.mocap_pos [n, nmocap, 3] and mocap_quat [n, nmocap, 4] as the caller wrote them (the
         kernel normalises the quaternion it reads); rows by body_mocapid"""
-        n = self.n - env0 if n is None else n
         nm = self.model.nmocap
-        pos = np.empty((n, nm, 3), dtype=np.float64)
-        quat = np.empty((n, nm, 4), dtype=np.float64)
-        _check(lib().mrs_batch_get_mocap(self._h, pos.ctypes.data, quat.ctypes.data, env0, n))
-        return pos, quat
+        return tuple(self._get_rows(lib().mrs_batch_get_mocap, (), [(nm, 3), (nm, 4)], env0, n))
 
     def set_mocap(self, pos=None, quat=None, env0: int = 0) -> None:
         """write the mocap poses of envs [env0, env0 + n); a part given as None is left as it is"""
         nm = self.model.nmocap
-        if nm == 0 or (pos is None and quat is None):
-            return
-        p = None if pos is None else np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, nm, 3)
-        q = None if quat is None else np.ascontiguousarray(quat, dtype=np.float64).reshape(-1, nm, 4)
-        if p is not None and q is not None and p.shape[0] != q.shape[0]:
-            raise ValueError("pos and quat cover different numbers of envs")
-        n = (p if p is not None else q).shape[0]
-        _check(lib().mrs_batch_set_mocap(self._h, None if p is None else p.ctypes.data,
-                                         None if q is None else q.ctypes.data, env0, n))
+        self._set_rows(lib().mrs_batch_set_mocap, (), [(nm, 3), (nm, 4)], [pos, quat], env0)
 
     def mocap_pos_device_ptr(self) -> int:
         """mocap_pos on the device, fp32 [n, nmocap, 3], ordered on the batch stream (0 when nmocap == 0)"""
@@ -473,25 +469,19 @@ class Batch:
     def get_model_param(self, param: int, env0: int = 0, n: int | None = None) -> np.ndarray:
         """per-env model parameter PARAM_*: actuator gainprm / biasprm [0:3] as [n, nu, 3], dof damping
         [n, nv], geom sliding friction [n, ngeom]; the model's own values until the parameter is set"""
-        n = self.n - env0 if n is None else n
-        shape = self._param_shape(param)
-        out = np.empty((max(n, 0),) + shape, dtype=np.float64)
-        _check(lib().mrs_batch_get_param(self._h, param, out.ctypes.data, env0, n))
-        return out
+        # (clamp: a negative n is the library's to reject)
+        return self._get_rows(lib().mrs_batch_get_param, (param,), [self._param_shape(param)], env0, n, clamp=True)[0]
 
     def set_model_param(self, param: int, values, env0: int = 0) -> None:
         """write a model parameter of envs [env0, env0 + n); one row of values broadcasts over the envs
         from env0 on.  Takes effect at the next step / forward launch; resets keep it"""
         shape = self._param_shape(param)
-        if 0 in shape:  # e.g. gainprm of a model without actuators
-            return
         a = np.asarray(values, dtype=np.float64)
         if a.ndim == len(shape):
             a = np.broadcast_to(a, (self.n - env0,) + shape)
-        a = np.ascontiguousarray(a).reshape((-1,) + shape)
         if a.size == 0:
             return
-        _check(lib().mrs_batch_set_param(self._h, param, a.ctypes.data, env0, a.shape[0]))
+        self._set_rows(lib().mrs_batch_set_param, (param,), [shape], [a], env0)
 
     def model_param_device_ptr(self, param: int) -> int:
         """the parameter's buffer on the device, fp32 [n_envs, dim], ordered on the batch stream (made on
