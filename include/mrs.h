@@ -82,6 +82,16 @@ int mrs_model_view_get(const mrs_model* m, mrs_model_view* out);
 /* opt into this restatement's own solver variants (MRS_RESTATE_* bits of mrs_model.h; 0, the
  * default, follows the upstream rules); batches created afterwards use them */
 int mrs_model_set_restate(mrs_model* m, int flags);
+/* the constants mj_setConst derives from mass / inertia / armature at qpos0; any input NULL = the
+ * model's own; any output NULL = not wanted.  body_mass [nbody], body_inertia [nbody][3] (principal
+ * moments in the body's compiled body_iquat frame), dof_armature [nv]; outputs body_subtreemass [nbody],
+ * dof_M0 [nv], dof_invweight0 [nv], body_invweight0 [nbody][2], meaninertia [1].  The function the MJCF
+ * compiler itself calls, so the model's own inputs return the model's own constants.  No GPU needed.
+ * MRS_ERR_INVALID for a non-finite or negative input or when M(qpos0) is not positive definite;
+ * MRS_ERR_UNSUPPORTED for a model with tendons (tendon_invweight0 is not re-derived yet). */
+int mrs_model_derive_inertial(const mrs_model* m, const double* body_mass, const double* body_inertia,
+                              const double* dof_armature, double* body_subtreemass, double* dof_M0,
+                              double* dof_invweight0, double* body_invweight0, double* meaninertia);
 /* replaces mj_name2id (src/mujoco_system_interface.cpp:1193,1213,1496-1497,1527-1529);
  * objtype is MRS_OBJ_*; returns -1 if not found */
 int mrs_name2id(const mrs_model* m, int objtype, const char* name);
@@ -222,6 +232,36 @@ int mrs_batch_get_param(mrs_batch* b, int param, double* host, int env0, int n);
  * ordered on the batch stream takes effect at the next step / forward launch.  Writes through it are not
  * checked.  NULL when dim == 0 or on error (mrs_last_status). */
 float* mrs_batch_param_device_ptr(mrs_batch* b, int param);
+
+/* ---- per-env body mass, inertia and dof armature (no reference counterpart).  A family of its own, not
+ * MRS_PARAM_* values: these have derived constants in the compiled model, and a write is exactly "set
+ * those mjModel arrays, then mj_setConst" -- the env then steps as a model whose body_subtreemass,
+ * dof_M0, stat_meaninertia, dof_invweight0 and body_invweight0 were derived from the new values at
+ * qpos0 (and whose friction-loss rows' regulariser and solver scale follow).  body_ipos / body_iquat
+ * stay the model's; body_inertia is the principal moments in the compiled body_iquat frame.  Two
+ * exceptions: a kv that the compiler derived from dampratio keeps its compiled value (mj_setConst does
+ * not redo it either; MRS_PARAM_ACT_BIASPRM moves it), and a model with tendons is refused with
+ * MRS_ERR_UNSUPPORTED (tendon_invweight0 is a follow-up).  Model values: mrs_batch_reset, both masked
+ * resets and the NaN auto-reset leave them alone; they hold over the n steps of a launch and RK4's
+ * stages.  Row 0 (the world) is ignored on write and reads back the model's.  There is no
+ * device-pointer call: a raw device write would leave the derived constants stale. */
+enum { MRS_INERTIAL_BODY_MASS = 0, MRS_INERTIAL_BODY_INERTIA = 1, MRS_INERTIAL_DOF_ARMATURE = 2,
+       MRS_INERTIAL_COUNT = 3 };
+int mrs_batch_inertial_dim(const mrs_batch* b, int which);             /* nbody, 3 nbody, nv */
+/* host rows [n][dim] fp64 for envs [env0, env0+n); a NULL pointer leaves that quantity as it is.
+ * One re-derivation per env per call (host, fp64, the compiler's own function; the results are rounded
+ * to fp32 as the model block is).  The per-env storage is made on the first set; before that
+ * get_inertial returns the model's values and no launch takes any per-env code.  MRS_ERR_INVALID for a
+ * non-finite or negative value and for a row whose M(qpos0) is not positive definite (for example zero
+ * mass and inertia on a moving body with zero armature); a rejected call writes nothing for any env. */
+int mrs_batch_set_inertial(mrs_batch* b, const double* mass, const double* inertia,
+                           const double* armature, int env0, int n);
+int mrs_batch_get_inertial(mrs_batch* b, double* mass, double* inertia, double* armature, int env0, int n);
+/* what the kernels read for env `env` (fp32 on the device, widened): for tests and debugging.
+ * body_subtreemass [nbody], dof_invweight0 [nv], body_invweight0 [nbody][2], meaninertia [1] (from the
+ * stored solver scale 1 / (meaninertia max(1, nv))); any output NULL = not wanted */
+int mrs_batch_get_inertial_derived(mrs_batch* b, int env, double* body_subtreemass, double* dof_invweight0,
+                                   double* body_invweight0, double* meaninertia);
 
 /* replaces mj_step (src/mujoco_system_interface.cpp:1691,1731): advance every env n_steps times,
  * fused in one launch; ctrl / qfrc_applied are held constant (zero-order hold) across the n steps,

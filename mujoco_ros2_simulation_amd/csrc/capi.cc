@@ -1,13 +1,16 @@
 // C ABI (include/mrs.h): exception firewall + handle management.  Every entry point catches, stores
 // the message in a thread-local buffer (mrs_last_error) and returns an MRS_ERR_* code or NULL.
+#include <algorithm>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/mrs.h"
 #include "hip/batch.h"
 #include "mjcf/model.h"
+#include "hip/start_rows.h"
 #include "mjcf/xml.h"
 
 struct mrs_model {
@@ -127,6 +130,32 @@ int mrs_model_view_get(const mrs_model* m, mrs_model_view* out) {
   return guarded([&] {
     if (!m || !out) throw std::invalid_argument("null argument");
     *out = m->m.view();
+  });
+}
+
+int mrs_model_derive_inertial(const mrs_model* m, const double* body_mass, const double* body_inertia,
+                              const double* dof_armature, double* body_subtreemass, double* dof_M0,
+                              double* dof_invweight0, double* body_invweight0, double* meaninertia) {
+  return guarded([&] {
+    if (!m) throw std::invalid_argument("null model");
+    const mrs::Model& mm = m->m;
+    if (!mm.tendon_adr.empty()) throw mrs::UnsupportedError("inertial re-derivation of a model with tendons (tendon_invweight0)");
+    const double* mass = body_mass ? body_mass : mm.body_mass.data();
+    const double* inertia = body_inertia ? body_inertia : mm.body_inertia.data();
+    const double* armature = dof_armature ? dof_armature : mm.dof_armature.data();
+    mrs::check_inertial_values(mm, mass, inertia, armature);
+    mrs::setconst::InertialConst c;
+    try {
+      mrs::setconst::derive_inertial(mm, mass, inertia, armature, c);
+    } catch (const std::runtime_error&) {
+      throw std::invalid_argument("M(qpos0) is not positive definite for these inertial values");
+    }
+    auto put = [](double* dst, const std::vector<double>& v) { if (dst) std::copy(v.begin(), v.end(), dst); };
+    put(body_subtreemass, c.body_subtreemass);
+    put(dof_M0, c.dof_M0);
+    put(dof_invweight0, c.dof_invweight0);
+    put(body_invweight0, c.body_invweight0);
+    if (meaninertia) *meaninertia = c.meaninertia;
   });
 }
 
@@ -325,6 +354,38 @@ float* mrs_batch_param_device_ptr(mrs_batch* b, int param) {
     p = mrs::batch_param_device_ptr(b->impl, param);
   });
   return p;
+}
+
+int mrs_batch_inertial_dim(const mrs_batch* b, int which) {
+  int dim = MRS_ERR_INVALID;
+  const int rc = guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    dim = mrs::batch_inertial_dim(b->impl, which);
+  });
+  return rc == MRS_OK ? dim : rc;
+}
+
+int mrs_batch_set_inertial(mrs_batch* b, const double* mass, const double* inertia, const double* armature,
+                           int env0, int n) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_set_inertial(b->impl, mass, inertia, armature, env0, n);
+  });
+}
+
+int mrs_batch_get_inertial(mrs_batch* b, double* mass, double* inertia, double* armature, int env0, int n) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_get_inertial(b->impl, mass, inertia, armature, env0, n);
+  });
+}
+
+int mrs_batch_get_inertial_derived(mrs_batch* b, int env, double* body_subtreemass, double* dof_invweight0,
+                                   double* body_invweight0, double* meaninertia) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_get_inertial_derived(b->impl, env, body_subtreemass, dof_invweight0, body_invweight0, meaninertia);
+  });
 }
 
 int mrs_batch_step(mrs_batch* b, int n_steps) {

@@ -42,6 +42,13 @@ int batch_param_dim(BatchImpl* b, int param);
 void batch_set_param(BatchImpl* b, int param, const double* host, int env0, int n);
 void batch_get_param(BatchImpl* b, int param, double* host, int env0, int n);
 float* batch_param_device_ptr(BatchImpl* b, int param);
+// per-env body mass / inertia / dof armature (MRS_INERTIAL_*): host rows [n][dim], a null part is left
+// as it is; every set re-derives the env's constants on the host (start_rows.h inertial_row)
+int batch_inertial_dim(BatchImpl* b, int which);
+void batch_set_inertial(BatchImpl* b, const double* mass, const double* inertia, const double* armature, int env0, int n);
+void batch_get_inertial(BatchImpl* b, double* mass, double* inertia, double* armature, int env0, int n);
+void batch_get_inertial_derived(BatchImpl* b, int env, double* body_subtreemass, double* dof_invweight0,
+                                double* body_invweight0, double* meaninertia);
 void batch_set_ctrl_device(BatchImpl* b, const float* d_ctrl);
 void batch_bind_ctrl_device(BatchImpl* b, const float* d_ctrl);  // zero-copy ctrl source (null: own buffer)
 void batch_set_timing(BatchImpl* b, int mask);  // launches timed for batch_last_kernel_ms (bit 0 step, 1 frames)

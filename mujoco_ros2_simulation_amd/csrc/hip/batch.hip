@@ -14,6 +14,7 @@
 #include <initializer_list>
 #include <stdexcept>
 #include <string>
+#include <thread>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -982,6 +983,9 @@ struct BatchImpl {
   // their upload, which the masked reset (reset_masked_kernel) reads, next to the runtime pool [pool_n]
   // of batch_set_start_states (capacity pool_cap rows)
   StartRows start;
+  // the envs' mass / inertia / armature as the caller wrote them, fp64 [n][4 nbody + nv] (empty until the
+  // first set_inertial): what a later set of one quantity re-derives the others from, and get_inertial reads
+  std::vector<double> inr_host;
   float *tab_qpos = nullptr, *tab_qvel = nullptr, *tab_ctrl = nullptr, *tab_act = nullptr;
   float *tab_mpos = nullptr, *tab_mquat = nullptr;  // the mocap poses' rows (row 0: the bodies' pos / quat)
   double* tab_time = nullptr;
@@ -1183,7 +1187,7 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
   d.timestep = static_cast<float>(m.timestep);
   d.timestep_d = m.timestep;
   d.tolerance = static_cast<float>(m.tolerance);
-  d.pgs_scale = static_cast<float>(1.0 / (m.stat_meaninertia * std::max(1, m.nv)));
+  d.pgs_scale = solver_scale(m.stat_meaninertia, m.nv);
   for (int i = 0; i < 3; ++i) d.gravity[i] = static_cast<float>(m.gravity[i]);
 
   // --- host precomputation of flat lists
@@ -1583,12 +1587,9 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
     auto fbits = [](int v) { float f; std::memcpy(&f, &v, sizeof f); return f; };
     auto clampf = [](float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); };
     for (int j : fric) {
-      const float si0 = static_cast<float>(m.dof_solimp[5 * j]), si1 = static_cast<float>(m.dof_solimp[5 * j + 1]);
-      const float width = static_cast<float>(m.dof_solimp[5 * j + 2]);
-      const float dmin = clampf(si0, 0.0001f, 0.9999f), dmax = clampf(si1, 0.0001f, 0.9999f);
-      const float imp = (dmin == dmax || width <= 1e-15f) ? 0.5f * (dmin + dmax) : dmin;
-      float R = (1 - imp) * static_cast<float>(m.dof_invweight0[j]) / imp;
-      R = R > 1e-15f ? R : 1e-15f;
+      const float si1 = static_cast<float>(m.dof_solimp[5 * j + 1]);
+      const float dmax = clampf(si1, 0.0001f, 0.9999f);
+      const float R = fric_row_R(m, j, m.dof_invweight0[j]);  // (start_rows.h: an env's inertial row computes it too)
       const float sr0 = static_cast<float>(m.dof_solref[2 * j]), sr1 = static_cast<float>(m.dof_solref[2 * j + 1]);
       float B;
       if (sr0 > 0) {
@@ -2299,12 +2300,12 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
 // DevModel: the table points at that slot and keeps no copy), its elements per env, their type and
 // when the array is made -- and creation, the row copies and the accessors below all go by it.
 // Ids: the MRS_FIELD_* values, then
-enum { kArrAct = MRS_FIELD_COUNT, kArrMocapPos, kArrMocapQuat, kArrParam0, kArrCount = kArrParam0 + MRS_PARAM_COUNT };
+enum { kArrAct = MRS_FIELD_COUNT, kArrMocapPos, kArrMocapQuat, kArrParam0, kArrInertial = kArrParam0 + MRS_PARAM_COUNT, kArrCount };
 
 struct EnvArray {
   enum Type { F32, I32, F64 } type;
   // AT_CREATE: with the batch, a buffer even when dim == 0; IF_DIM: with the batch, null when dim == 0;
-  // ON_USE: null until first used (ensure_xfrc, ensure_param)
+  // ON_USE: null until first used (ensure_xfrc, ensure_param, ensure_inertial)
   enum Made { AT_CREATE, IF_DIM, ON_USE } made;
   int dim;     // elements per env; -1: no such array
   void* ptr;   // the array as its slot holds it now (null: not made)
@@ -2346,6 +2347,7 @@ EnvArray env_array(BatchImpl& b, int id) {
     case kArrParam0 + MRS_PARAM_ACT_BIASPRM: return env_array_at(d.prm_bias, 3 * m.nu, EnvArray::ON_USE);
     case kArrParam0 + MRS_PARAM_DOF_DAMPING: return env_array_at(d.prm_damp, m.nv, EnvArray::ON_USE);
     case kArrParam0 + MRS_PARAM_GEOM_FRICTION: return env_array_at(d.prm_fric, m.ngeom, EnvArray::ON_USE);
+    case kArrInertial: return env_array_at(d.prm_inr, inertial_layout(m).dim, EnvArray::ON_USE);
   }
   return {EnvArray::F32, EnvArray::ON_USE, -1, nullptr, nullptr};
 }
@@ -2462,6 +2464,36 @@ float* ensure_param(BatchImpl& b, int param) {
   a.bind(p);
   b.dm.prm_mask |= 1 << param;
   HIP_CHECK(hipMemcpy(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice));
+  return p;
+}
+
+// the inertial rows [n][dim] (start_rows.h inertial_layout: mass, inertia, armature and the constants
+// derived from them), made on the first set_inertial and filled with the model's own row for every env;
+// from then on the step kernel reads them (DevModel::prm_inr, bit kPrmInr of prm_mask).  Like ensure_param
+float* ensure_inertial(BatchImpl& b) {
+  const EnvArray a = env_array(b, kArrInertial);
+  if (a.ptr) return static_cast<float*>(a.ptr);
+  HIP_CHECK(hipSetDevice(b.device));
+  const Model& m = *b.model;
+  const std::vector<float> row = inertial_model_row(m, inertial_layout(m));
+  std::vector<float> all(static_cast<size_t>(b.n) * a.dim);
+  for (int e = 0; e < b.n; ++e) std::copy(row.begin(), row.end(), all.begin() + static_cast<size_t>(e) * a.dim);
+  float* p = static_cast<float*>(dalloc(b, all.size() * sizeof(float)));
+  HIP_CHECK(hipStreamSynchronize(b.stream));
+  HIP_CHECK(hipMemcpy(p, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
+  a.bind(p);
+  b.dm.inr_dim = a.dim;
+  b.dm.prm_mask |= kPrmInr;
+  HIP_CHECK(hipMemcpy(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice));
+  // the host's fp64 copy of the inputs starts from the model's too
+  const size_t hd = 4 * static_cast<size_t>(m.nbody) + m.nv;
+  b.inr_host.resize(static_cast<size_t>(b.n) * hd);
+  for (int e = 0; e < b.n; ++e) {
+    double* h = b.inr_host.data() + e * hd;
+    std::copy(m.body_mass.begin(), m.body_mass.end(), h);
+    std::copy(m.body_inertia.begin(), m.body_inertia.end(), h + m.nbody);
+    std::copy(m.dof_armature.begin(), m.dof_armature.end(), h + 4 * m.nbody);
+  }
   return p;
 }
 
@@ -2798,6 +2830,105 @@ void batch_get_param(BatchImpl* b, int param, double* host, int env0, int n) {
 }
 
 float* batch_param_device_ptr(BatchImpl* b, int param) { return ensure_param(*b, param); }
+
+int batch_inertial_dim(BatchImpl* b, int which) {
+  const Model& m = *b->model;
+  switch (which) {
+    case MRS_INERTIAL_BODY_MASS: return m.nbody;
+    case MRS_INERTIAL_BODY_INERTIA: return 3 * m.nbody;
+    case MRS_INERTIAL_DOF_ARMATURE: return m.nv;
+  }
+  throw std::invalid_argument("unknown inertial quantity");
+}
+
+void batch_set_inertial(BatchImpl* b, const double* mass, const double* inertia, const double* armature, int env0, int n) {
+  const Model& m = *b->model;
+  if (!m.tendon_adr.empty()) throw UnsupportedError("per-env mass / inertia / armature on a model with tendons (tendon_invweight0)");
+  check_env_range(*b, env0, n);
+  if (n == 0 || (!mass && !inertia && !armature)) return;
+  const int nb = m.nbody, nv = m.nv;
+  const size_t hd = 4 * static_cast<size_t>(nb) + nv;
+  // the envs' new inputs: what they hold now (the model's before the first set), the given quantities
+  // substituted, the world's row kept.  Checked and derived before anything is made or written
+  std::vector<double> in(static_cast<size_t>(n) * hd);
+  for (int e = 0; e < n; ++e) {
+    double* h = in.data() + e * hd;
+    if (!b->inr_host.empty()) {
+      std::copy_n(b->inr_host.data() + (static_cast<size_t>(env0) + e) * hd, hd, h);
+    } else {
+      std::copy(m.body_mass.begin(), m.body_mass.end(), h);
+      std::copy(m.body_inertia.begin(), m.body_inertia.end(), h + nb);
+      std::copy(m.dof_armature.begin(), m.dof_armature.end(), h + 4 * nb);
+    }
+    if (mass) std::copy_n(mass + static_cast<size_t>(e) * nb + 1, nb - 1, h + 1);
+    if (inertia) std::copy_n(inertia + static_cast<size_t>(e) * 3 * nb + 3, 3 * (nb - 1), h + nb + 3);
+    if (armature) std::copy_n(armature + static_cast<size_t>(e) * nv, nv, h + 4 * nb);
+    check_inertial_values(m, h, h + nb, h + 4 * nb);
+  }
+  // one re-derivation per env (host, fp64; linear in n), over at most 16 threads for large ranges
+  const InertialLayout l = inertial_layout(m);
+  std::vector<double> rows(static_cast<size_t>(n) * l.dim);
+  auto derive = [&](int e0, int e1) {
+    for (int e = e0; e < e1; ++e) {
+      const double* h = in.data() + e * hd;
+      const std::vector<float> r = inertial_row(m, l, h, h + nb, h + 4 * nb);
+      std::copy(r.begin(), r.end(), rows.begin() + static_cast<size_t>(e) * l.dim);
+    }
+  };
+  const int nthreads = std::min(16, n / 64);
+  if (nthreads < 2) {
+    derive(0, n);
+  } else {
+    std::vector<std::thread> pool;
+    std::vector<std::exception_ptr> err(nthreads);
+    for (int t = 0; t < nthreads; ++t)
+      pool.emplace_back([&, t] {
+        try {
+          derive(static_cast<int>(static_cast<long long>(n) * t / nthreads), static_cast<int>(static_cast<long long>(n) * (t + 1) / nthreads));
+        } catch (...) {
+          err[t] = std::current_exception();
+        }
+      });
+    for (std::thread& t : pool) t.join();
+    for (const std::exception_ptr& e : err) if (e) std::rethrow_exception(e);
+  }
+  ensure_inertial(*b);
+  std::copy(in.begin(), in.end(), b->inr_host.begin() + static_cast<size_t>(env0) * hd);
+  rows_to_device(*b, env0, n, {{env_array(*b, kArrInertial), rows.data()}});
+}
+
+void batch_get_inertial(BatchImpl* b, double* mass, double* inertia, double* armature, int env0, int n) {
+  const Model& m = *b->model;
+  check_env_range(*b, env0, n);
+  const int nb = m.nbody, nv = m.nv;
+  const size_t hd = 4 * static_cast<size_t>(nb) + nv;
+  for (int e = 0; e < n; ++e) {
+    // never set: the model's values for every env
+    const double* h = b->inr_host.empty() ? nullptr : b->inr_host.data() + (static_cast<size_t>(env0) + e) * hd;
+    if (mass) std::copy_n(h ? h : m.body_mass.data(), nb, mass + static_cast<size_t>(e) * nb);
+    if (inertia) std::copy_n(h ? h + nb : m.body_inertia.data(), 3 * nb, inertia + static_cast<size_t>(e) * 3 * nb);
+    if (armature) std::copy_n(h ? h + 4 * nb : m.dof_armature.data(), nv, armature + static_cast<size_t>(e) * nv);
+  }
+}
+
+void batch_get_inertial_derived(BatchImpl* b, int env, double* body_subtreemass, double* dof_invweight0,
+                                double* body_invweight0, double* meaninertia) {
+  const Model& m = *b->model;
+  check_env_range(*b, env, 1);
+  const InertialLayout l = inertial_layout(m);
+  const EnvArray a = env_array(*b, kArrInertial);
+  std::vector<double> row(l.dim);
+  if (a.ptr) {
+    rows_to_host(*b, env, 1, {{a, row.data()}});
+  } else {  // never set: the model's own row, and no buffer made
+    const std::vector<float> r = inertial_model_row(m, l);
+    std::copy(r.begin(), r.end(), row.begin());
+  }
+  if (body_subtreemass) std::copy_n(row.data() + l.subtreemass, m.nbody, body_subtreemass);
+  if (dof_invweight0) std::copy_n(row.data() + l.dof_invweight0, m.nv, dof_invweight0);
+  if (body_invweight0) std::copy_n(row.data() + l.body_invweight0, 2 * m.nbody, body_invweight0);
+  if (meaninertia) *meaninertia = 1.0 / (row[l.pgs_scale] * std::max(1, m.nv));
+}
 
 void batch_bind_ctrl_device(BatchImpl* b, const float* d_ctrl) { b->ctrl_bound = d_ctrl; }
 

@@ -258,10 +258,19 @@ struct DevModel {
   // staged into the workgroup-shared tables, which are the same for every env
   const float *prm_gain, *prm_bias, *prm_damp, *prm_fric;
   int npair_explicit;  // the explicit <contact><pair> entries, first in the pair list
+  // per-env body mass / inertia / dof armature and the constants derived from them (MRS_INERTIAL_*;
+  // DESIGN.md §3.16): null until the first set_inertial (batch.hip ensure_inertial; bit kPrmInr of
+  // prm_mask is set with it).  [n_envs][inr_dim] fp32, one row per env (start_rows.h InertialLayout):
+  // mass [nbody], inertia [3 nbody], armature [nv], body_subtreemass [nbody], dof_invweight0 [nv],
+  // body_invweight0 [2 nbody], the friction-loss rows' R [nfric], pgs_scale [1].  The lane group's row
+  // is the one xfrc_row uses.  Kept last: the fields above keep their offsets
+  const float* prm_inr;
+  int inr_dim;
 };
 constexpr int kRayBlock = 128;
 // bits of DevModel::prm_mask (1 << MRS_PARAM_*)
 constexpr int kPrmGain = 1, kPrmBias = 2, kPrmDamp = 4, kPrmFric = 8;
+constexpr int kPrmInr = 16;  // the inertial rows (prm_inr) are in use
 
 // waves per workgroup: 256-thread workgroups with lane groups (G < 64); one wave (one env) per
 // workgroup at G = 64, so LDS is granted per env (the C5 working set of ~13.5 KB fits 11 envs per

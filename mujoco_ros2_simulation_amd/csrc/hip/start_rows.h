@@ -5,10 +5,13 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
+#include <stdexcept>
 #include <vector>
 
 #include "../../../include/mrs.h"
 #include "../mjcf/model.h"
+#include "../mjcf/setconst.h"
 
 namespace mrs {
 
@@ -68,6 +71,99 @@ inline std::vector<float> param_model_row(const Model& m, int param) {
       break;
   }
   return r;
+}
+
+// ---- per-env body mass / inertia / dof armature and the constants derived from them (MRS_INERTIAL_*;
+// DESIGN.md §3.16).  One fp32 row per env, inputs first, then what mj_setConst derives from them:
+//   mass [nbody] | inertia [3 nbody] | armature [nv] | body_subtreemass [nbody] | dof_invweight0 [nv] |
+//   body_invweight0 [2 nbody] | R of each friction-loss dof's row [nfric] | pgs_scale [1]
+// step.hip reads the row by these offsets (inr_* there).
+struct InertialLayout {
+  int mass, inertia, armature, subtreemass, dof_invweight0, body_invweight0, fric_R, pgs_scale, dim;
+};
+inline int num_fric_dofs(const Model& m) {
+  int n = 0;
+  for (int j = 0; j < m.nv; ++j) n += m.dof_frictionloss[j] > 0;
+  return n;
+}
+inline InertialLayout inertial_layout(const Model& m) {
+  InertialLayout l;
+  l.mass = 0;
+  l.inertia = m.nbody;
+  l.armature = 4 * m.nbody;
+  l.subtreemass = l.armature + m.nv;
+  l.dof_invweight0 = l.subtreemass + m.nbody;
+  l.body_invweight0 = l.dof_invweight0 + m.nv;
+  l.fric_R = l.body_invweight0 + 2 * m.nbody;
+  l.pgs_scale = l.fric_R + num_fric_dofs(m);
+  l.dim = l.pgs_scale + 1;
+  return l;
+}
+
+// the regulariser R of dof j's friction-loss row (distance 0 at margin 0, so a model constant) from the
+// dof's invweight0, in fp32 and in the order the kernel's row_impedance computes it: the one expression
+// behind the shared fricrec table and an env's inertial row
+inline float fric_row_R(const Model& m, int j, double dof_invweight0) {
+  auto clampf = [](float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); };
+  const float si0 = static_cast<float>(m.dof_solimp[5 * j]), si1 = static_cast<float>(m.dof_solimp[5 * j + 1]);
+  const float width = static_cast<float>(m.dof_solimp[5 * j + 2]);
+  const float dmin = clampf(si0, 0.0001f, 0.9999f), dmax = clampf(si1, 0.0001f, 0.9999f);
+  const float imp = (dmin == dmax || width <= 1e-15f) ? 0.5f * (dmin + dmax) : dmin;
+  float R = (1 - imp) * static_cast<float>(dof_invweight0) / imp;
+  R = R > 1e-15f ? R : 1e-15f;
+  return R;
+}
+// the PGS stop test's / primal solvers' scale, as the model block holds it
+inline float solver_scale(double meaninertia, int nv) {
+  return static_cast<float>(1.0 / (meaninertia * std::max(1, nv)));
+}
+
+// finite and non-negative, in fp32 too (what set_inertial and mrs_model_derive_inertial check before
+// anything is derived or written); row 0 (the world) is not looked at by the callers that ignore it
+inline void check_inertial_values(const Model& m, const double* mass, const double* inertia, const double* armature) {
+  auto check = [](const double* v, int n) {
+    for (int i = 0; v && i < n; ++i) {
+      if (!std::isfinite(v[i]) || !std::isfinite(static_cast<float>(v[i])))
+        throw std::invalid_argument("inertial value is not finite");
+      if (v[i] < 0) throw std::invalid_argument("negative mass, inertia or armature");
+    }
+  };
+  check(mass, m.nbody);
+  check(inertia, 3 * m.nbody);
+  check(armature, m.nv);
+}
+
+// an env's inertial row from its fp64 mass / inertia / armature: the constants by the compiler's own
+// function (setconst.h), each rounded to fp32 exactly as the model block is packed, so the model's own
+// values give the values the shared tables hold.  Throws std::invalid_argument when M(qpos0) is not
+// positive definite
+inline std::vector<float> inertial_row(const Model& m, const InertialLayout& l, const double* mass, const double* inertia,
+                                       const double* armature) {
+  setconst::InertialConst c;
+  try {
+    setconst::derive_inertial(m, mass, inertia, armature, c);
+  } catch (const std::runtime_error&) {
+    throw std::invalid_argument("M(qpos0) is not positive definite for these inertial values");
+  }
+  std::vector<float> r(l.dim);
+  for (int b = 0; b < m.nbody; ++b) {
+    r[l.mass + b] = static_cast<float>(mass[b]);
+    for (int i = 0; i < 3; ++i) r[l.inertia + 3 * b + i] = static_cast<float>(inertia[3 * b + i]);
+    r[l.subtreemass + b] = static_cast<float>(c.body_subtreemass[b]);
+    for (int i = 0; i < 2; ++i) r[l.body_invweight0 + 2 * b + i] = static_cast<float>(c.body_invweight0[2 * b + i]);
+  }
+  int k = 0;
+  for (int j = 0; j < m.nv; ++j) {
+    r[l.armature + j] = static_cast<float>(armature[j]);
+    r[l.dof_invweight0 + j] = static_cast<float>(c.dof_invweight0[j]);
+    if (m.dof_frictionloss[j] > 0) r[l.fric_R + k++] = fric_row_R(m, j, c.dof_invweight0[j]);
+  }
+  r[l.pgs_scale] = solver_scale(c.meaninertia, m.nv);
+  return r;
+}
+// the model's own inertial row: what every env holds until it is set
+inline std::vector<float> inertial_model_row(const Model& m, const InertialLayout& l) {
+  return inertial_row(m, l, m.body_mass.data(), m.body_inertia.data(), m.dof_armature.data());
 }
 
 }  // namespace mrs

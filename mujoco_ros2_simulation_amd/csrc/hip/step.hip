@@ -2027,6 +2027,48 @@ __device__ __forceinline__ void chol_solve_serial(const lfloat* Lf, int nv, cons
   }
 }
 
+// kPrm: this kernel carries the per-env model reads (MRS_PRM; the parameters' functions are further down)
+constexpr bool kPrm = MRS_PRM != 0;
+__device__ float prm_env(const float* base, const gfloat* scr, int slot, int dim, int i, float own);
+// ---- per-env body mass / inertia / dof armature and the constants derived from them (MRS_INERTIAL_*;
+// DESIGN.md §3.16): value i of the group's inertial row (DevModel::prm_inr; the offsets below are
+// start_rows.h InertialLayout), behind the scalar test of kPrmInr, the load out of line like the
+// parameters'.  `own` is the model's value, kept by an idle group and by every kernel without MRS_PRM
+__device__ __forceinline__ float inr_val(const DevModel& m, const gfloat* scr, int i, float own) {
+  if (kPrm && (m.prm_mask & kPrmInr)) { [[clang::noinline]] own = prm_env(m.prm_inr, scr, m.S.xfrc, m.inr_dim, i, own); }
+  return own;
+}
+__device__ __forceinline__ float body_mass_env(const DevModel& m, const gfloat* scr, int b, float own) {
+  return inr_val(m, scr, b, own);
+}
+// principal moment k of body b
+__device__ __forceinline__ float body_inertia_env(const DevModel& m, const gfloat* scr, int b, int k, float own) {
+  return inr_val(m, scr, m.nbody + 3 * b + k, own);
+}
+__device__ __forceinline__ float dof_armature_env(const DevModel& m, const gfloat* scr, int j, float own) {
+  return inr_val(m, scr, 4 * m.nbody + j, own);
+}
+__device__ __forceinline__ float body_subtreemass_env(const DevModel& m, const gfloat* scr, int b, float own) {
+  return inr_val(m, scr, 4 * m.nbody + m.nv + b, own);
+}
+// every read of dof_invweight0[j] and body_invweight0[i] (i = 2 body + translation / rotation) goes
+// through these two
+__device__ __forceinline__ float dof_invweight0(const DevModel& m, const gfloat* scr, int j) {
+  return inr_val(m, scr, 5 * m.nbody + m.nv + j, m.dof_invweight0[j]);
+}
+__device__ __forceinline__ float body_invweight0(const DevModel& m, const gfloat* scr, int i) {
+  return inr_val(m, scr, 5 * m.nbody + 2 * m.nv + i, m.body_invweight0[i]);
+}
+// the regulariser of friction-loss row k (fricrec[4 k + 1], a model constant through dof_invweight0)
+__device__ __forceinline__ float fric_R_env(const DevModel& m, const gfloat* scr, int k, float own) {
+  return inr_val(m, scr, 7 * m.nbody + 2 * m.nv + k, own);
+}
+// 1 / (meaninertia max(1, nv)): the PGS stop tests' and the primal solvers' scale; every read of
+// pgs_scale goes through here
+__device__ __forceinline__ float solver_scale(const DevModel& m, const gfloat* scr) {
+  return inr_val(m, scr, 7 * m.nbody + 2 * m.nv + m.nfric, m.pgs_scale);
+}
+
 // Smooth-dynamics tables (batch.hip actrec, dofrec, bodytab, mpairtab): from workgroup LDS with lane
 // groups, from the model block in blocked mode (G = 64, where LDS is per env)
 template <int G>
@@ -2137,9 +2179,23 @@ __device__ __forceinline__ void body_pose(const DevModel& m, lfloat* s, int b, c
 
 // body frame outputs: xpos, xquat, xmat, inertial frame and the rotational part of cinert
 template <int G>
-__device__ __forceinline__ void body_frame_out(const DevModel& m, lfloat* s, int b, const float pos[3], float q[4]) {
+__device__ __forceinline__ void body_frame_out(const DevModel& m, lfloat* s, const gfloat* scr, int b, const float pos[3], float q[4]) {
   const LdsLayout& L = m.L;
   const auto kb = kin_body<G>(m, b);
+  // the principal moments, per env in the MRS_PRM kernels.  Read here, before any of the frame's
+  // arithmetic, and the env's mass left in cinert[9] for com_pos (which overwrites that slot with the mass
+  // anyway): a branch in the middle of either function's arithmetic splits its basic block, the compiler
+  // then contracts the products and sums on either side differently, and a batch that set the model's own
+  // values would no longer step bit for bit like one that set nothing
+  float I0 = kb[14], I1 = kb[15], I2 = kb[16];
+  if constexpr (kPrm) {
+    float bm = body_tab<G>(m, b)[0];
+    if (m.prm_mask & kPrmInr) {
+      I0 = body_inertia_env(m, scr, b, 0, I0); I1 = body_inertia_env(m, scr, b, 1, I1); I2 = body_inertia_env(m, scr, b, 2, I2);
+      bm = body_mass_env(m, scr, b, bm);
+    }
+    s[L.cinert + 10 * b + 9] = bm;
+  }
   quat_normalize(q);
   float xm[9];
   quat2mat(xm, q);
@@ -2154,7 +2210,6 @@ __device__ __forceinline__ void body_frame_out(const DevModel& m, lfloat* s, int
   for (int i = 0; i < 3; ++i) s[L.xipos + 3 * b + i] = pos[i] + r[i];
   quat_mul(qi, q, iq);
   quat2mat(R, qi);
-  const float I0 = kb[14], I1 = kb[15], I2 = kb[16];
   lfloat* ci = s + L.cinert + 10 * b;
   ci[0] = R[0] * I0 * R[0] + R[1] * I1 * R[1] + R[2] * I2 * R[2];
   ci[1] = R[3] * I0 * R[3] + R[4] * I1 * R[4] + R[5] * I2 * R[5];
@@ -2176,7 +2231,7 @@ __device__ void kinematics_levels(ENV_PARAMS) {
   const float P0[3] = {0, 0, 0};
     if (lane == 0) {
       float q1[4] = {1, 0, 0, 0};
-      body_frame_out<G>(m, s, 0, P0, q1);
+      body_frame_out<G>(m, s, scr, 0, P0, q1);
     }
     wsync();
     for (int lev = 1; lev <= m.max_depth; ++lev) {
@@ -2189,7 +2244,7 @@ __device__ void kinematics_levels(ENV_PARAMS) {
         const float Q[4] = {s[L.xquat + 4 * p], s[L.xquat + 4 * p + 1], s[L.xquat + 4 * p + 2], s[L.xquat + 4 * p + 3]};
         float pos[3], q[4];
         body_pose<G, true>(m, s, b, P, Q, pos, q);
-        body_frame_out<G>(m, s, b, pos, q);
+        body_frame_out<G>(m, s, scr, b, pos, q);
       }
       wsync();
     }
@@ -2253,10 +2308,10 @@ __device__ MRS_PHASE void kinematics(ENV_PARAMS) {
           }
           for (int i = 0; i < 3; ++i) { s[L.xanchor + 3 * j + i] = anc[i]; s[L.xaxis + 3 * j + i] = ax[i]; }
         }
-        body_frame_out<G>(m, s, b, pos, q);
+        body_frame_out<G>(m, s, scr, b, pos, q);
       } else if (b == 0) {
         float q1[4] = {1, 0, 0, 0};
-        body_frame_out<G>(m, s, 0, P0, q1);
+        body_frame_out<G>(m, s, scr, 0, P0, q1);
       }
       wsync();
     } else {
@@ -2270,10 +2325,10 @@ __device__ MRS_PHASE void kinematics(ENV_PARAMS) {
     wsync();
     if (b >= 1 && b < m.nbody) {
       body_pose<G, true>(m, s, b, P, Q, pos, q);
-      body_frame_out<G>(m, s, b, pos, q);
+      body_frame_out<G>(m, s, scr, b, pos, q);
     } else if (b == 0) {
       float q1[4] = {1, 0, 0, 0};
-      body_frame_out<G>(m, s, 0, P0, q1);
+      body_frame_out<G>(m, s, scr, 0, P0, q1);
     }
     wsync();
     }
@@ -2310,10 +2365,10 @@ __device__ MRS_PHASE void com_pos(ENV_PARAMS) {
     const int e = __float_as_int(bt[4]);
     #pragma unroll 4
     for (int k = b; k < e; ++k) {
-      const float mk = body_tab<G>(m, k)[0];
+      const float mk = body_mass_env(m, scr, k, body_tab<G>(m, k)[0]);
       for (int i = 0; i < 3; ++i) c[i] += mk * s[L.xipos + 3 * k + i];
     }
-    const float sm = bt[1];
+    const float sm = body_subtreemass_env(m, scr, b, bt[1]);
     for (int i = 0; i < 3; ++i) s[L.scom + 3 * b + i] = sm > kMinVal ? c[i] / sm : s[L.xipos + 3 * b + i];
   }
   wsync();
@@ -2323,7 +2378,7 @@ __device__ MRS_PHASE void com_pos(ENV_PARAMS) {
     if (b == 0) { for (int i = 0; i < 10; ++i) ci[i] = 0; continue; }
     const auto bt = body_tab<G>(m, b);
     const int rt = __float_as_int(bt[2]);
-    const float mass = bt[0];
+    const float mass = kPrm ? (float)ci[9] : (float)bt[0];  // (MRS_PRM: the env's, left by body_frame_out)
     float d[3];
     for (int i = 0; i < 3; ++i) d[i] = s[L.xipos + 3 * b + i] - s[L.scom + 3 * rt + i];
     ci[0] += mass * (d[1] * d[1] + d[2] * d[2]);
@@ -2395,6 +2450,7 @@ __device__ MRS_PHASE void make_M(ENV_PARAMS) {
     for (int k = 0; k < 6; ++k) cd[k] = s[L.cdof + 6 * i + k];
     mul_inert_vec(buf, s + L.crb + 10 * __float_as_int(mp4[2]), cd);
     float v = mp4[3];
+    if (kPrm && i == j) v = dof_armature_env(m, scr, i, v);
     for (int k = 0; k < 6; ++k) v += s[L.cdof + 6 * j + k] * buf[k];
     s[L.M + midx<G>(m, i, j)] = v;
     s[L.M + midx<G>(m, j, i)] = v;
@@ -2653,7 +2709,7 @@ __device__ __forceinline__ const gfloat* xfrc_row(const DevModel& m, const gfloa
 // workgroup-shared tables.  They take their arguments by value: a DevModel reference into an
 // out-of-line function would put the caller's whole model copy on the stack.
 
-constexpr bool kPrm = MRS_PRM != 0;
+// (kPrm: defined with the inertial reads, before the kinematics)
 // value i of the group's row of a parameter buffer [n_envs][dim]; an idle group (row -1) reads
 // nothing and keeps the model's `own`
 __device__ __forceinline__ float prm_at(const float* base, const gfloat* scr, int slot, int dim, int i, float own) {
@@ -2906,7 +2962,8 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS) {
           const float gc = m.body_gravcomp[b];
           if (gc == 0) continue;
           float f[3], col[3], pnt[3] = {s[L.xipos + 3 * b], s[L.xipos + 3 * b + 1], s[L.xipos + 3 * b + 2]};
-          for (int i = 0; i < 3; ++i) f[i] = -m.gravity[i] * m.body_mass[b] * gc;
+          const float bm = body_mass_env(m, scr, b, m.body_mass[b]);
+          for (int i = 0; i < 3; ++i) f[i] = -m.gravity[i] * bm * gc;
           jac_col(m, s, b, pnt, j, col);
           pas += dot3(col, f);
         }
@@ -3120,7 +3177,7 @@ __device__ __forceinline__ float sel_slot16(float own, float other) {
 template <bool kUnit = false, int KR = 16, int KV = 16, bool kRegAR = false>
 __device__ __forceinline__ float pgs_small16(const DevModel& m, lfloat* s, const gfloat* J, gfloat* ff, int nefc, int rmax,
                                              float myR, float myaref, float myb, float myfl, float qacc_s,
-                                             int lane, int mydof = -1) {
+                                             float pscale, int lane, int mydof = -1) {
   const LdsLayout& L = m.L;
   const int nv = m.nv;
   // instantiated per row count KR (the wave's rmax rounded up to 4 at the call site): rows past the
@@ -3283,7 +3340,7 @@ __device__ __forceinline__ float pgs_small16(const DevModel& m, lfloat* s, const
       myhi -= dm;
       const float improvement = gsum<16>(lane < rmax ? myA * dm * (gb - 0.5f * dm) : 0.0f);
       nit = it + 1;
-      if (improvement * m.pgs_scale < m.tolerance) break;
+      if (improvement * pscale < m.tolerance) break;
     }
   };
   if (KR <= 4 || rmax <= 4) sweeps(std::integral_constant<int, (KR < 4 ? KR : 4)>{});
@@ -3318,7 +3375,7 @@ __device__ __forceinline__ float pgs_small16(const DevModel& m, lfloat* s, const
 template <bool kUnit = false, int KR = 16>
 __device__ __forceinline__ float pgs_small16_qacc(const DevModel& m, lfloat* s, const gfloat* J, gfloat* ff, int nefc, int rmax,
                                              float myR, float myaref, float myb, float myfl, float qacc_s,
-                                             int lane, int mydof = -1, unsigned fmask = 0) {
+                                             float pscale, int lane, int mydof = -1, unsigned fmask = 0) {
   const LdsLayout& L = m.L;
   const int nv = m.nv;
   // kUnit (dof friction-loss rows): row r is the unit vector of dof r, held in lane r (rows indexed by
@@ -3448,7 +3505,7 @@ __device__ __forceinline__ float pgs_small16_qacc(const DevModel& m, lfloat* s, 
       }
     });
     nit = it + 1;
-    if (improvement * m.pgs_scale < m.tolerance) break;
+    if (improvement * pscale < m.tolerance) break;
   }
   if (lane == 0) s[L.niter] = __int_as_float(nit);
   float qc = 0;
@@ -3975,16 +4032,16 @@ __device__ float constraints_sparse(ENV_PARAMS, int ncon, float qacc_s) {
       float diag, mu = 0, bound = -1;
       int dim = 1;
       if (t == EFC_FRICTION) {
-        sr = m.dof_solref + 2 * id; si = m.dof_solimp + 5 * id; diag = m.dof_invweight0[id];
+        sr = m.dof_solref + 2 * id; si = m.dof_solimp + 5 * id; diag = dof_invweight0(m, scr, id);
         bound = floss[r0];
       } else if (t == EFC_LIMIT) {
-        sr = m.jnt_solref + 2 * id; si = m.jnt_solimp + 5 * id; diag = m.dof_invweight0[m.jnt_dofadr[id]];
+        sr = m.jnt_solref + 2 * id; si = m.jnt_solimp + 5 * id; diag = dof_invweight0(m, scr, m.jnt_dofadr[id]);
       } else {
         const int p = __float_as_int(scr[S.con + kConRec * id]);
         dim = m.pair_dim[p];
         mu = pair_mu(m, scr, p);  // sliding, for both tangent directions
         sr = m.pair_solref + 2 * p; si = m.pair_solimp + 5 * p;
-        const float tran = m.body_invweight0[2 * m.geom_bodyid[m.pair_g1[p]]] + m.body_invweight0[2 * m.geom_bodyid[m.pair_g2[p]]];
+        const float tran = body_invweight0(m, scr, 2 * m.geom_bodyid[m.pair_g1[p]]) + body_invweight0(m, scr, 2 * m.geom_bodyid[m.pair_g2[p]]);
         // pyramid edges: diagApprox tran (1 + mu^2), regulariser scaled by 2 mu^2 / impratio
         // (mj_makeImpedance; oracle/oracle.c make_constraint)
         diag = dim == 3 ? tran * (1 + mu * mu) * (2 * mu * mu / m.impratio) : tran;
@@ -4328,6 +4385,7 @@ __device__ float constraints_sparse(ENV_PARAMS, int ncon, float qacc_s) {
       // together after the sweep: a level is med3 + DPP broadcast + the FMAs + one select.  Levels run
       // in chunks of 16 (levels past nlev hold neutral rows: zero AR rows, step 0).
       int nit = 0;
+      const float pscale = solver_scale(m, scr);
       #pragma unroll 1
       for (int it = 0; it < m.iterations; ++it) {
         float gb[NJ];
@@ -4365,7 +4423,7 @@ __device__ float constraints_sparse(ENV_PARAMS, int ncon, float qacc_s) {
         });
         const float improvement = gsum<64>(imp);
         nit = it + 1;
-        if (improvement * m.pgs_scale < m.tolerance) break;
+        if (improvement * pscale < m.tolerance) break;
       }
       if (lane == 0) s[L.niter] = __int_as_float(nit);
       SUB_ADD(PH_CON_PGS, t_sub);
@@ -4531,6 +4589,7 @@ __device__ float constraints_sparse(ENV_PARAMS, int ncon, float qacc_s) {
       // PGS sweeps, one item at a time
       int slot_v = slot;
       int nit = 0;
+      const float pscale = solver_scale(m, scr);
       #pragma unroll 1
       for (int it = 0; it < m.iterations; ++it) {
 #pragma unroll
@@ -4570,7 +4629,7 @@ __device__ float constraints_sparse(ENV_PARAMS, int ncon, float qacc_s) {
         });
         improvement = gsum<64>(slot_v == 0 ? improvement : 0.0f);
         nit = it + 1;
-        if (improvement * m.pgs_scale < m.tolerance) break;
+        if (improvement * pscale < m.tolerance) break;
       }
       if (lane == 0) s[L.niter] = __int_as_float(nit);
       wsync();
@@ -4697,6 +4756,7 @@ __device__ float constraints_sparse(ENV_PARAMS, int ncon, float qacc_s) {
       // PGS sweeps
       int slot_v = slot;
       int nit = 0;  // sweeps done (mjData.solver_niter)
+      const float pscale = solver_scale(m, scr);
       #pragma unroll 1
       for (int it = 0; it < m.iterations; ++it) {
         // opaque per sweep: keeps the per-level dof indices and lane masks from being hoisted out
@@ -4725,7 +4785,7 @@ __device__ float constraints_sparse(ENV_PARAMS, int ncon, float qacc_s) {
         });
         improvement = gsum<64>(slot_v == 0 ? improvement : 0.0f);
         nit = it + 1;
-        if (improvement * m.pgs_scale < m.tolerance) break;
+        if (improvement * pscale < m.tolerance) break;
       }
       if (lane == 0) s[L.niter] = __int_as_float(nit);
       wsync();
@@ -4800,6 +4860,7 @@ __device__ float constraints_sparse(ENV_PARAMS, int ncon, float qacc_s) {
 
   // --- 5. PGS sweeps: level k = the k-th row of every pipe; next level's record prefetched
   int nit = 0;  // sweeps done (mjData.solver_niter)
+  const float pscale = solver_scale(m, scr);
   #pragma unroll 1
   for (int it = 0; it < m.iterations; ++it) {
     float improvement = 0;
@@ -4826,7 +4887,7 @@ __device__ float constraints_sparse(ENV_PARAMS, int ncon, float qacc_s) {
     improvement = gsum<64>(slot == 0 ? improvement : 0.0f);
     wsync();
     nit = it + 1;
-    if (improvement * m.pgs_scale < m.tolerance) break;
+    if (improvement * pscale < m.tolerance) break;
   }
   if (lane == 0) s[L.niter] = __int_as_float(nit);
   wsync();
@@ -5149,7 +5210,7 @@ __device__ float solve_primal(ENV_PARAMS, int nefc, bool newton) {
   gfloat* st = scr + S.efc_MJ;
   gfloat* ff = scr + S.efc_f;
   lfloat* xb = s + L.qacc;
-  const float scale = m.pgs_scale;
+  const float scale = solver_scale(m, scr);
   const float qs = dof ? s[L.qacc_smooth + lane] : 0.0f;
   const float fs = dof ? s[L.qfrc_smooth + lane] : 0.0f;
   auto is_fric = [&](int r) { return fric_like(__float_as_int(type[r]) >> 16); };
@@ -5532,7 +5593,7 @@ __device__ __forceinline__ float primal_small16(ENV_PARAMS, const gfloat* J, gfl
   });
   // row `lane` of M (LDS; zero past nv, where x is zero too)
   auto mrow = [&](int k) { return (k < nv && dof) ? (float)s[L.M + lane * nv + k] : 0.0f; };
-  const float scale = m.pgs_scale;
+  const float scale = solver_scale(m, scr);
   // lane r: J_r x (KR independent row reductions)
   auto rows_dot = [&](float x) {
     float out = 0;
@@ -5781,7 +5842,7 @@ __device__ MRS_PHASE float constraints(ENV_PARAMS, int ncon, float qacc_s, int p
         if (myk >= 0) {
           // the row's model constants from workgroup LDS (batch.hip fricrec: dof, R, B, frictionloss)
           const lfloat* fr = shared_lds(m) + m.shr_fric + 4 * myk;
-          myR = fr[1];
+          myR = fric_R_env(m, scr, myk, fr[1]);
           myaref = -fr[2] * s[L.qvel + lane];  // friction rows have no position term
           myb = s[L.qacc_smooth + lane] - myaref;
           myfl = fr[3];
@@ -5801,9 +5862,9 @@ __device__ MRS_PHASE float constraints(ENV_PARAMS, int ncon, float qacc_s, int p
       }
       // dofs unrolled to 8 when the model has at most 8: a quarter of the substitution code
       if (m.nv <= 8)
-        qa = pgs_small16_qacc<true, 8>(m, s, nullptr, scr + S.efc_f, nf, 8, myR, myaref, myb, myfl, qacc_s, lane, myk, fmask);
+        qa = pgs_small16_qacc<true, 8>(m, s, nullptr, scr + S.efc_f, nf, 8, myR, myaref, myb, myfl, qacc_s, solver_scale(m, scr), lane, myk, fmask);
       else
-        qa = pgs_small16_qacc<true, 16>(m, s, nullptr, scr + S.efc_f, nf, 16, myR, myaref, myb, myfl, qacc_s, lane, myk, fmask);
+        qa = pgs_small16_qacc<true, 16>(m, s, nullptr, scr + S.efc_f, nf, 16, myR, myaref, myb, myfl, qacc_s, solver_scale(m, scr), lane, myk, fmask);
       wsync();
       return qa;
     }
@@ -5842,9 +5903,9 @@ __device__ __forceinline__ void row_impedance(const DevModel& m, const lfloat* s
   const int t = code >> 16, id = code & 0xffff;
   CPtr<float> sr, si;
   float diag;
-  if (t == EFC_FRICTION) { sr = m.dof_solref + 2 * id; si = m.dof_solimp + 5 * id; diag = m.dof_invweight0[id]; }
+  if (t == EFC_FRICTION) { sr = m.dof_solref + 2 * id; si = m.dof_solimp + 5 * id; diag = dof_invweight0(m, scr, id); }
   else if (t == EFC_EQUALITY) { sr = m.eq_solref + 2 * id; si = m.eq_solimp + 5 * id; diag = bb[r]; }
-  else if (t == EFC_LIMIT) { sr = m.jnt_solref + 2 * id; si = m.jnt_solimp + 5 * id; diag = m.dof_invweight0[m.jnt_dofadr[id]]; }
+  else if (t == EFC_LIMIT) { sr = m.jnt_solref + 2 * id; si = m.jnt_solimp + 5 * id; diag = dof_invweight0(m, scr, m.jnt_dofadr[id]); }
   else if (t == EFC_TFRICTION) { sr = m.ten_solref_fri + 2 * id; si = m.ten_solimp_fri + 5 * id; diag = m.ten_prm[12 * id + 8]; }
   else if (t == EFC_TLIMIT) { sr = m.ten_solref_lim + 2 * id; si = m.ten_solimp_lim + 5 * id; diag = m.ten_prm[12 * id + 8]; }
   else {
@@ -5852,7 +5913,7 @@ __device__ __forceinline__ void row_impedance(const DevModel& m, const lfloat* s
     const int p = __float_as_int(rec[0]);
     sr = m.pair_solref + 2 * p; si = m.pair_solimp + 5 * p;
     const int b1 = m.geom_bodyid[m.pair_g1[p]], b2 = m.geom_bodyid[m.pair_g2[p]];
-    float tran = m.body_invweight0[2 * b1] + m.body_invweight0[2 * b2];
+    float tran = body_invweight0(m, scr, 2 * b1) + body_invweight0(m, scr, 2 * b2);
     diag = tran;
     if (m.pair_dim[p] == 3 && m.cone == MRS_CONE_ELLIPTIC) {
       // elliptic: diagApprox tran for every row of the block, the tangents' regulariser / impratio
@@ -5933,14 +5994,14 @@ __device__ int dense_rows(ENV_PARAMS, int ncon) {
     if (t == MRS_EQ_JOINT) {
       const int d1 = m.jnt_dofadr[o1];
       const float x1 = s[L.qpos + m.jnt_qposadr[o1]] - dd[5];
-      float poly = dd[0], dpoly = 0, diag = m.dof_invweight0[d1];
+      float poly = dd[0], dpoly = 0, diag = dof_invweight0(m, scr, d1);
       int d2 = -1;
       if (o2 >= 0) {
         d2 = m.jnt_dofadr[o2];
         const float x = s[L.qpos + m.jnt_qposadr[o2]] - dd[6];
         poly = dd[0] + x * (dd[1] + x * (dd[2] + x * (dd[3] + x * dd[4])));
         dpoly = dd[1] + x * (2 * dd[2] + x * (3 * dd[3] + x * 4 * dd[4]));
-        diag += m.dof_invweight0[d2];
+        diag += dof_invweight0(m, scr, d2);
       }
       if (lane < nv) J[nefc * nv + lane] = (lane == d1 ? 1.0f : 0.0f) - (lane == d2 ? dpoly : 0.0f);
       if (lane == 0) {
@@ -5978,7 +6039,7 @@ __device__ int dense_rows(ENV_PARAMS, int ncon) {
       jac_col(m, s, o1, p1, lane, c1);
       jac_col(m, s, o2, p2, lane, c2);
     }
-    const float tdiag = m.body_invweight0[2 * o1] + m.body_invweight0[2 * o2];
+    const float tdiag = body_invweight0(m, scr, 2 * o1) + body_invweight0(m, scr, 2 * o2);
     for (int k = 0; k < 3; ++k) {
       if (lane < nv) J[nefc * nv + lane] = c1[k] - c2[k];
       if (lane == 0) {
@@ -6003,7 +6064,7 @@ __device__ int dense_rows(ENV_PARAMS, int ncon) {
       quat_mul(tq, cq, wv);
       quat_mul(de, tq, q2);
     }
-    const float rdiag = m.body_invweight0[2 * o1 + 1] + m.body_invweight0[2 * o2 + 1];
+    const float rdiag = body_invweight0(m, scr, 2 * o1 + 1) + body_invweight0(m, scr, 2 * o2 + 1);
     for (int k = 0; k < 3; ++k) {
       if (lane < nv) J[nefc * nv + lane] = 0.5f * de[1 + k] * ts;
       if (lane == 0) {
@@ -6345,12 +6406,13 @@ __device__ float constraints_dense(ENV_PARAMS, int ncon, float qacc_s, int pre_n
     if (small) {
       // rows unrolled to the wave's row count, the substitutions to the model's dof count (nv can
       // exceed the row count: a free body with one contact, an arm with one active limit)
+      const float pscale = solver_scale(m, scr);
       auto solve = [&](auto kv) {
         constexpr int KV = decltype(kv)::value;
-        if (rmax <= 4) return pgs_small16<false, 4, KV, kHot>(m, s, J, ff, nefc, rmax, my_R, my_aref, my_b, my_fl, qacc_s, lane);
-        if (rmax <= 8) return pgs_small16<false, 8, KV, kHot>(m, s, J, ff, nefc, rmax, my_R, my_aref, my_b, my_fl, qacc_s, lane);
-        if (rmax <= 12) return pgs_small16<false, 12, KV, kHot>(m, s, J, ff, nefc, rmax, my_R, my_aref, my_b, my_fl, qacc_s, lane);
-        return pgs_small16<false, 16, KV, kHot>(m, s, J, ff, nefc, rmax, my_R, my_aref, my_b, my_fl, qacc_s, lane);
+        if (rmax <= 4) return pgs_small16<false, 4, KV, kHot>(m, s, J, ff, nefc, rmax, my_R, my_aref, my_b, my_fl, qacc_s, pscale, lane);
+        if (rmax <= 8) return pgs_small16<false, 8, KV, kHot>(m, s, J, ff, nefc, rmax, my_R, my_aref, my_b, my_fl, qacc_s, pscale, lane);
+        if (rmax <= 12) return pgs_small16<false, 12, KV, kHot>(m, s, J, ff, nefc, rmax, my_R, my_aref, my_b, my_fl, qacc_s, pscale, lane);
+        return pgs_small16<false, 16, KV, kHot>(m, s, J, ff, nefc, rmax, my_R, my_aref, my_b, my_fl, qacc_s, pscale, lane);
       };
       float qa = nv <= 8 ? solve(std::integral_constant<int, 8>{}) : solve(std::integral_constant<int, 16>{});
       wsync();
@@ -6435,6 +6497,7 @@ __device__ float constraints_dense(ENV_PARAMS, int ncon, float qacc_s, int pre_n
     for (int r = lane; r < nefc; r += G) fd[r] = ff[r];
     wsync();
     double qd = lane < nv ? static_cast<double>(qa) : 0.0;
+    const float pscale = solver_scale(m, scr);
     #pragma unroll 1
     for (int it = 0; it < m.iterations; ++it) {
       double improvement = 0;
@@ -6487,7 +6550,7 @@ __device__ float constraints_dense(ENV_PARAMS, int ncon, float qacc_s, int pre_n
         wsync();
       }
       nit = it + 1;
-      if (improvement * m.pgs_scale < m.tolerance) break;
+      if (improvement * pscale < m.tolerance) break;
     }
     if (lane == 0) s[L.niter] = __int_as_float(nit);
     // qfrc_constraint = J' f; the row forces exported in fp32 (mrs_batch_get_efc)
@@ -6502,6 +6565,7 @@ __device__ float constraints_dense(ENV_PARAMS, int ncon, float qacc_s, int pre_n
     wsync();
     return static_cast<float>(qd);
   }
+  const float pscale = solver_scale(m, scr);
   #pragma unroll 1
   for (int it = 0; it < m.iterations; ++it) {
     float improvement = 0;
@@ -6524,7 +6588,7 @@ __device__ float constraints_dense(ENV_PARAMS, int ncon, float qacc_s, int pre_n
       wsync();
     }
     nit = it + 1;
-    if (improvement * m.pgs_scale < m.tolerance) break;
+    if (improvement * pscale < m.tolerance) break;
   }
   if (lane == 0) s[L.niter] = __int_as_float(nit);
   // --- qfrc_constraint = J' f
@@ -7410,11 +7474,11 @@ __device__ void sensors_more(ENV_PARAMS, gfloat* sensordata, int ncon) {
     float o0 = 0, o1 = 0, o2 = 0;
     if (t == MRS_SENS_SUBTREECOM || t == MRS_SENS_SUBTREELINVEL) {
       const int e = __float_as_int(sr[15]);
-      const float sm = sr[20];
+      const float sm = body_subtreemass_env(m, scr, b, sr[20]);
       const bool vel = t == MRS_SENS_SUBTREELINVEL;
       #pragma unroll 1
       for (int k = b; k < e; ++k) {
-        const float mk = m.body_mass[k];
+        const float mk = body_mass_env(m, scr, k, m.body_mass[k]);
         float x0 = s[L.xipos + 3 * k], x1 = s[L.xipos + 3 * k + 1], x2 = s[L.xipos + 3 * k + 2];
         if (vel) {
           // the body com's velocity: cvel moved from the tree's com to xipos

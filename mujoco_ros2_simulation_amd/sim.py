@@ -36,6 +36,8 @@ RESTATE_NEWTON_REFINE, RESTATE_PGS_ELLIPTIC_BLOCK, RESTATE_NO_MPR_POLISH, RESTAT
 (FIELD_QPOS, FIELD_QVEL, FIELD_CTRL, FIELD_QFRC_APPLIED, FIELD_QACC_WARMSTART, FIELD_QACC,
  FIELD_QFRC_ACTUATOR, FIELD_SENSORDATA, FIELD_TIME, FIELD_WARNING, FIELD_NCON, FIELD_SOLVER_NITER,
  FIELD_XFRC_APPLIED) = range(13)
+# per-env body mass / inertia / dof armature (MRS_INERTIAL_*; Batch.get_inertial / set_inertial)
+INERTIAL_BODY_MASS, INERTIAL_BODY_INERTIA, INERTIAL_DOF_ARMATURE, INERTIAL_COUNT = 0, 1, 2, 3
 # per-env model parameters (MRS_PARAM_*; Batch.get_model_param / set_model_param)
 PARAM_ACT_GAINPRM, PARAM_ACT_BIASPRM, PARAM_DOF_DAMPING, PARAM_GEOM_FRICTION = range(4)
 # ActuatorType (include/mujoco_ros2_control/data.hpp:43-51 numbering)
@@ -247,6 +249,12 @@ def lib() -> C.CDLL:
         L.mrs_batch_get_param.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.mrs_batch_param_device_ptr.restype = C.c_void_p
         L.mrs_batch_param_device_ptr.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "mrs_batch_set_inertial"):  # (an A/B library named by MRS_LIB may predate the family)
+            L.mrs_model_derive_inertial.argtypes = [C.c_void_p] + [C.c_void_p] * 8
+            L.mrs_batch_inertial_dim.argtypes = [C.c_void_p, C.c_int]
+            L.mrs_batch_set_inertial.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+            L.mrs_batch_get_inertial.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+            L.mrs_batch_get_inertial_derived.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mrs_batch_set_ctrl_device.argtypes = [C.c_void_p, C.c_void_p]
         L.mrs_batch_bind_ctrl_device.argtypes = [C.c_void_p, C.c_void_p]
         L.mrs_batch_set_timing.argtypes = [C.c_void_p, C.c_int]
@@ -350,6 +358,25 @@ class Model:
         _check(lib().mrs_model_set_restate(self._h, int(flags)))
         _check(lib().mrs_model_view_get(self._h, C.byref(self.view)))
         self.restate = self.view.restate
+
+    def derive_inertial(self, body_mass=None, body_inertia=None, dof_armature=None) -> dict:
+        """the constants mj_setConst derives at qpos0 from body_mass [nbody], body_inertia [nbody, 3] and
+        dof_armature [nv] (None: the model's own), by the compiler's own function: body_subtreemass,
+        dof_M0, dof_invweight0, body_invweight0 [nbody, 2] and meaninertia.  No GPU needed"""
+        def arg(v, shape):
+            if v is None:
+                return None
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            if a.shape != shape:
+                raise ValueError(f"expected shape {shape}, got {a.shape}")
+            return a
+        ins = [arg(body_mass, (self.nbody,)), arg(body_inertia, (self.nbody, 3)), arg(dof_armature, (self.nv,))]
+        out = {"body_subtreemass": np.zeros(self.nbody), "dof_M0": np.zeros(self.nv), "dof_invweight0": np.zeros(self.nv),
+               "body_invweight0": np.zeros((self.nbody, 2)), "meaninertia": np.zeros(1)}
+        _check(lib().mrs_model_derive_inertial(self._h, *(None if a is None else a.ctypes.data for a in ins),
+                                               *(o.ctypes.data for o in out.values())))
+        out["meaninertia"] = float(out["meaninertia"][0])
+        return out
 
     def name2id(self, objtype: int, name: str) -> int:
         return lib().mrs_name2id(self._h, objtype, name.encode())
@@ -487,6 +514,44 @@ class Batch:
         """the parameter's buffer on the device, fp32 [n_envs, dim], ordered on the batch stream (made on
         first use; 0 when the model has none of it)"""
         return lib().mrs_batch_param_device_ptr(self._h, param) or 0
+
+    def _inertial_shapes(self) -> list:
+        return [(self.model.nbody,), (self.model.nbody, 3), (self.model.nv,)]
+
+    def get_inertial(self, env0: int = 0, n: int | None = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """per-env body_mass [n, nbody], body_inertia [n, nbody, 3] and dof_armature [n, nv]; the model's own
+        values until set_inertial"""
+        return tuple(self._get_rows(lib().mrs_batch_get_inertial, (), self._inertial_shapes(), env0, n, clamp=True))
+
+    def set_inertial(self, mass=None, inertia=None, armature=None, env0: int = 0) -> None:
+        """write body mass / principal inertia / dof armature of envs [env0, env0 + n), as "set the mjModel
+        arrays, then mj_setConst": the envs' derived constants are re-derived on the host.  A quantity given
+        as None is left as it is; one row broadcasts over the envs from env0 on.  Resets keep the values"""
+        rows = []
+        for v, shape in zip([mass, inertia, armature], self._inertial_shapes()):
+            if v is None:
+                rows.append(None)
+                continue
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim == len(shape):
+                a = np.broadcast_to(a, (self.n - env0,) + shape)
+            rows.append(np.ascontiguousarray(a).reshape((-1,) + shape))
+        ns = {r.shape[0] for r in rows if r is not None}
+        if not ns:
+            return
+        if len(ns) > 1:
+            raise ValueError("mass, inertia and armature cover different numbers of envs")
+        _check(lib().mrs_batch_set_inertial(self._h, *(None if r is None else r.ctypes.data for r in rows), env0, ns.pop()))
+
+    def inertial_derived(self, env: int) -> dict:
+        """what the kernels read for env `env` (fp32 on the device, widened): body_subtreemass,
+        dof_invweight0, body_invweight0 [nbody, 2] and meaninertia"""
+        m = self.model
+        out = {"body_subtreemass": np.zeros(m.nbody), "dof_invweight0": np.zeros(m.nv),
+               "body_invweight0": np.zeros((m.nbody, 2)), "meaninertia": np.zeros(1)}
+        _check(lib().mrs_batch_get_inertial_derived(self._h, env, *(o.ctypes.data for o in out.values())))
+        out["meaninertia"] = float(out["meaninertia"][0])
+        return out
 
     def reset(self, key: int = -1, env0: int = 0, n: int | None = None) -> None:
         _check(lib().mrs_batch_reset(self._h, key, env0, self.n - env0 if n is None else n))
