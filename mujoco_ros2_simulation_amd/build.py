@@ -18,20 +18,32 @@ LIB = PKG / "libmrs.so"
 ARCH = os.environ.get("MRS_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["hip/step.hip", "hip/batch.hip"]
-# step.hip is compiled once per part (-DMRS_STEP_PART=n), in parallel: part 0 is the dispatcher, the
-# others each instantiate one group width's kernels (17: the G = 16 primal-solver kernel; 18 / 65: the
-# G = 16 / 64 kernels with the extended code, MRS_EXT -- MPR contact polish, > 32 ray geoms -- which
-# parts 16, 17, 19 and 64 leave out; 19: the G = 16 step kernels with ray helper waves)
-# 108 / 116 / 120 / 132 / 164: the G = 8 / 16 / 16 with helper waves / 32 / 64 kernels with the per-env
-# model parameter reads (MRS_PRM), launched only by batches that use one; every other part leaves them out
-STEP_PARTS = [0, 8, 16, 17, 18, 19, 32, 64, 65, 108, 116, 120, 132, 164]
-STEP_NO_EXT = {16, 17, 19, 64, 120}
-STEP_PRM = {108, 116, 120, 132, 164}
-
-
-def _part_flags(part: int) -> list[str]:
-    return [f"-DMRS_STEP_PART={part}", f"-DMRS_EXT={0 if part in STEP_NO_EXT else 1}",
-            f"-DMRS_PRM={1 if part in STEP_PRM else 0}"]
+# step.hip is compiled once per part, in parallel.  A part is the four properties of its row: the group
+# width G, the kernel set (step.hip kSel*: forward, step, the G = 16 primal-solver step, the G = 16 step
+# kernels with ray helper waves), MRS_EXT (the extended code: MPR contact polish, > 32 ray geoms) and
+# MRS_PRM (the per-env model parameter reads, launched only by batches that use one).  step.hip's
+# launch_step names the parts by these properties; the name here is the object file's only.
+FWD_STEP = "kSelForward | kSelStep"
+STEP_PARTS = [
+    # name               G   kernel set                  EXT PRM
+    ("g8",               8,  "kSelAll",                  1, 0),
+    ("g16",              16, FWD_STEP,                   0, 0),
+    ("g16_primal",       16, "kSelPrimal",               0, 0),
+    ("g16_ext",          16, FWD_STEP + " | kSelPrimal", 1, 0),
+    ("g16_helpers",      16, "kSelHelpers",              0, 0),
+    ("g32",              32, "kSelAll",                  1, 0),
+    ("g64",              64, "kSelAll",                  0, 0),
+    ("g64_ext",          64, "kSelAll",                  1, 0),
+    ("g8_prm",           8,  "kSelAll",                  1, 1),
+    ("g16_prm",          16, FWD_STEP + " | kSelPrimal", 1, 1),
+    ("g16_helpers_prm",  16, "kSelHelpers",              0, 1),
+    ("g32_prm",          32, "kSelAll",                  1, 1),
+    ("g64_prm",          64, "kSelAll",                  1, 1),
+]
+# (object name suffix, flags) of every step.hip unit: the dispatcher, "part0", then the parts
+STEP_UNITS = [("part0", ["-DMRS_DISPATCH"])] + [
+    (f"part_{name}", [f"-DMRS_PART_G={g}", f"-DMRS_PART_SEL=({sel})", f"-DMRS_EXT={ext}", f"-DMRS_PRM={prm}"])
+    for name, g, sel, ext, prm in STEP_PARTS]
 # fp32 division/sqrt via v_rcp/v_sqrt (<= 2.5 ulp) instead of the correctly-rounded sequences:
 # the parity tolerance is 1e-5 relative, and the ray/contact math is division-heavy
 HIP_FLAGS = ["-fno-hip-fp32-correctly-rounded-divide-sqrt",
@@ -40,8 +52,10 @@ HIP_FLAGS = ["-fno-hip-fp32-correctly-rounded-divide-sqrt",
              # kernel; C3 +1.3 %, same-box A/B); values below 1.2e-38 do not occur in the step's state
              "-fgpu-flush-denormals-to-zero"]
 CXX_SOURCES = ["capi.cc", "mjcf/compiler.cc", "mjcf/mesh.cc", "mjcf/xml.cc"]
-HEADERS = ["hip/devmodel.h", "hip/batch.h", "hip/raymesh.h", "hip/start_rows.h", "mjcf/model.h", "mjcf/mesh.h", "mjcf/xml.h",
-           "mjcf/setconst.h"]
+# every header under csrc/hip is a dependency of every object: listed by glob, so that a new header
+# cannot be forgotten and leave a stale object
+HEADERS = sorted(str(h.relative_to(CSRC)) for h in (CSRC / "hip").glob("**/*.h")) + [
+    "mjcf/model.h", "mjcf/mesh.h", "mjcf/xml.h", "mjcf/setconst.h"]
 
 
 def _newer(src: Path, dst: Path, deps: list[Path]) -> bool:
@@ -72,16 +86,15 @@ def build_lib(verbose: bool = False) -> Path:
     OBJ.mkdir(parents=True, exist_ok=True)
     objs = []
     jobs = []
-    units = [(rel, None) for rel in HIP_SOURCES + CXX_SOURCES if rel != "hip/step.hip"]
-    units += [("hip/step.hip", part) for part in STEP_PARTS]
-    for rel, part in units:
+    units = [(rel, "", []) for rel in HIP_SOURCES + CXX_SOURCES if rel != "hip/step.hip"]
+    units += [("hip/step.hip", "." + suffix, flags) for suffix, flags in STEP_UNITS]
+    for rel, suffix, extra in units:
         src = CSRC / rel
-        obj = OBJ / (rel.replace("/", "_") + (f".part{part}" if part is not None else "") + ".o")
+        obj = OBJ / (rel.replace("/", "_") + suffix + ".o")
         objs.append(obj)
         if not _newer(src, obj, deps):
             continue
         if rel.endswith(".hip"):
-            extra = _part_flags(part) if part is not None else []
             cmd = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", *HIP_FLAGS, *extra, "-c", str(src),
                    "-o", str(obj)]
         else:
@@ -104,7 +117,7 @@ def build_lib(verbose: bool = False) -> Path:
 
 
 def build_variant(name: str, flags: list[str]) -> Path:
-    """an A/B variant libmrs_<name>.so: every step.hip part compiled with extra flags (e.g.
+    """an A/B variant libmrs_<name>.so: every step.hip unit compiled with extra flags (e.g.
     -DMRS_PHASE_TIMING), linked with the product's other objects (scripts/build_variant.sh)"""
     build_lib()
     vdir = OBJ / f"variant_{name}"
@@ -113,11 +126,10 @@ def build_variant(name: str, flags: list[str]) -> Path:
     objs, procs = [], []
     # the profiling build keeps one translation unit: its device-side phase counters
     # (g_phase_cycles) must be the one copy every kernel instantiation adds into
-    parts = [None] if "-DMRS_PHASE_TIMING" in flags else STEP_PARTS
-    for part in parts:
-        obj = vdir / f"step.part{part}.o"
+    units = [("single", [])] if "-DMRS_PHASE_TIMING" in flags else STEP_UNITS
+    for suffix, pflags in units:
+        obj = vdir / f"step.{suffix}.o"
         objs.append(obj)
-        pflags = [] if part is None else _part_flags(part)
         cmd = ["hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", *HIP_FLAGS, *pflags,
                *flags, "-c", str(src), "-o", str(obj)]
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

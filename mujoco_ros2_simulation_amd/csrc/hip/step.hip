@@ -17,7 +17,9 @@
 #include "raymesh.h"
 
 // MRS_EXT: compile the extended code paths (MPR contact polish, chunked ray pass for more than 32
-// ray geoms).  The split build sets it per part (build.py); one translation unit carries them.
+// ray geoms).  The split build sets it per part (build.py); one translation unit carries them.  Their
+// call sites alone cost the inlined G = 16 / 64 phases registers and scratch (C3 -1.3 % for the ray call
+// site), so models that do not need them run parts built without; the G = 8 / 32 parts always carry them
 #ifndef MRS_EXT
 #define MRS_EXT 1
 #endif
@@ -28,8 +30,20 @@
 #ifndef MRS_PRM
 #define MRS_PRM 1
 #endif
+// The split build (build.py STEP_PARTS) compiles this file once per part, in parallel.  A part is its
+// group width MRS_PART_G, its kernel set MRS_PART_SEL (the kSel* bits below) and its MRS_EXT and MRS_PRM;
+// it instantiates those kernels only.  One more unit, MRS_DISPATCH, holds launch_step and no kernel.
+// With neither flag this is a single translation unit with every kernel (scripts/build_variant.sh).
 
 namespace mrs {
+
+// kernel selection bits of launch_g
+constexpr int kSelForward = 1, kSelStep = 2, kSelPrimal = 4, kSelHelpers = 8, kSelAll = 15;
+#ifdef MRS_PART_SEL
+constexpr int kBuiltSel = MRS_PART_SEL;
+#else
+constexpr int kBuiltSel = kSelAll;
+#endif
 
 namespace {
 
@@ -7044,13 +7058,9 @@ __device__ void rays_chunked(ENV_PARAMS, gfloat* sensordata) {
   }
 }
 
-// the sweep code is left out of the helper-wave kernels' translation unit (they keep the block passes;
-// batch.hip never sets rf_sweep with helper waves)
-#if defined(MRS_STEP_PART) && (MRS_STEP_PART == 19 || MRS_STEP_PART == 120)
-constexpr bool kRaySweepBuilt = false;
-#else
-constexpr bool kRaySweepBuilt = true;
-#endif
+// the sweep code is left out of a translation unit that builds the helper-wave kernels alone (kBuiltSel;
+// they keep the block passes: batch.hip never sets rf_sweep with helper waves)
+constexpr bool kRaySweepBuilt = kBuiltSel != kSelHelpers;
 #ifndef MRS_SWEEP_ROWS
 #define MRS_SWEEP_ROWS 4
 #endif
@@ -8299,10 +8309,8 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
 
 }  // namespace
 
-// kernel selection bits of launch_g (the split build compiles each part in its own translation unit)
-constexpr int kSelForward = 1, kSelStep = 2, kSelPrimal = 4, kSelHelpers = 8, kSelAll = 15;
-
-template <int G, int kSel = kSelAll>
+// launch the kernel of group width G that the arguments ask for, of the set kSel this unit builds
+template <int G, int kSel>
 static void launch_g(const DevModel* d_model, int lds_floats, int shared_floats, const DevState& st, int n_envs,
                      int n_steps, bool forward_only, bool primal, hipStream_t stream) {
   const int wpb = G == 16 ? st.wpb16 : WavesPerBlock<G>::value;
@@ -8341,7 +8349,23 @@ static void launch_g(const DevModel* d_model, int lds_floats, int shared_floats,
   }
 }
 
-#if !defined(MRS_STEP_PART) || MRS_STEP_PART == 0
+#define MRS_LAUNCH_ARGS const DevModel* d_model, int lds_floats, int shared_floats, const DevState& st, int n_envs, \
+                        int n_steps, bool forward_only, bool primal, hipStream_t stream
+#define MRS_LAUNCH_PASS d_model, lds_floats, shared_floats, st, n_envs, n_steps, forward_only, primal, stream
+// One launch function per part of the split build, named by the part's properties: the dispatcher's
+// unit only declares it, each part's unit defines the one of its own flags, so a part that launch_step
+// names and build.py's table does not build fails the link.  kExt / kParams: the part's MRS_EXT / MRS_PRM
+template <int G, int kSel, bool kExt, bool kParams>
+void launch_part(MRS_LAUNCH_ARGS);
+#ifndef MRS_DISPATCH
+template <int G, int kSel, bool kExt, bool kParams>
+void launch_part(MRS_LAUNCH_ARGS) { launch_g<G, kSel>(MRS_LAUNCH_PASS); }
+#endif
+
+#ifdef MRS_PART_G
+// this part's: the one instantiation with the flags it was compiled with
+template void launch_part<MRS_PART_G, MRS_PART_SEL, MRS_EXT != 0, MRS_PRM != 0>(MRS_LAUNCH_ARGS);
+#else
 // profiling variant only: per-phase wave-cycle totals since the last reset (s_memtime ticks summed
 // over waves); returns the number of phases, 0 in normal builds
 int phase_cycles(double* out, int n, bool reset) {
@@ -8360,106 +8384,44 @@ int phase_cycles(double* out, int n, bool reset) {
 #endif
 }
 
-#endif
-
-#ifndef MRS_STEP_PART
-// single translation unit: every instantiation (the variant builds, scripts/build_variant.sh)
+// The one rule that picks a part.  ext: the model needs the extended code; params: a per-env model
+// parameter is in use (DevModel::prm_mask != 0).  batch.hip never combines helper waves with ext, so at
+// G = 16 the ext test comes first and the ext part carries no helper kernels.  (The single translation
+// unit instantiates every launch_part named here, with MRS_EXT and MRS_PRM as compiled.)
 hipError_t launch_step(const DevModel* d_model, int lds_floats, int shared_floats, const DevState& st, int n_envs,
                        int n_steps, bool forward_only, int group, bool primal, bool ext, bool params, hipStream_t stream) {
-  (void)ext; (void)params;  // (one translation unit: MRS_EXT and MRS_PRM as compiled)
-  switch (group) {
-    case 8: launch_g<8>(d_model, lds_floats, shared_floats, st, n_envs, n_steps, forward_only, primal, stream); break;
-    case 16: launch_g<16>(d_model, lds_floats, shared_floats, st, n_envs, n_steps, forward_only, primal, stream); break;
-    case 32: launch_g<32>(d_model, lds_floats, shared_floats, st, n_envs, n_steps, forward_only, primal, stream); break;
-    case 64: launch_g<64>(d_model, lds_floats, shared_floats, st, n_envs, n_steps, forward_only, primal, stream); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-#else
-// split build (build.py): step.hip is compiled once per part, in parallel, each part instantiating
-// only its own kernels; part 0 holds the dispatcher.  Parts 16 / 17 (G = 16 primal) / 64 are compiled
-// without the extended code (MRS_EXT 0: the MPR contact polish and the chunked pass of more than 32
-// ray geoms -- their call sites alone cost the inlined G = 16 / 64 phases registers and scratch: C3
-// -1.3% for the ray call site); models that need it run parts 18 (G = 16) / 65 (G = 64), and the
-// G = 8 / 32 parts always carry it
-#define MRS_LAUNCH_ARGS const DevModel* d_model, int lds_floats, int shared_floats, const DevState& st, int n_envs, \
-                        int n_steps, bool forward_only, bool primal, hipStream_t stream
-#define MRS_LAUNCH_PASS d_model, lds_floats, shared_floats, st, n_envs, n_steps, forward_only, primal, stream
-void launch_part_8(MRS_LAUNCH_ARGS);
-void launch_part_16(MRS_LAUNCH_ARGS);
-void launch_part_17(MRS_LAUNCH_ARGS);
-void launch_part_18(MRS_LAUNCH_ARGS);
-void launch_part_19(MRS_LAUNCH_ARGS);
-void launch_part_32(MRS_LAUNCH_ARGS);
-void launch_part_64(MRS_LAUNCH_ARGS);
-void launch_part_65(MRS_LAUNCH_ARGS);
-// the kernels with the per-env model parameter reads (MRS_PRM 1; 120 without, the others with the
-// extended code): G = 8, G = 16, G = 16 with helper waves, G = 32, G = 64
-void launch_part_108(MRS_LAUNCH_ARGS);
-void launch_part_116(MRS_LAUNCH_ARGS);
-void launch_part_120(MRS_LAUNCH_ARGS);
-void launch_part_132(MRS_LAUNCH_ARGS);
-void launch_part_164(MRS_LAUNCH_ARGS);
-#if MRS_STEP_PART == 0
-hipError_t launch_step(const DevModel* d_model, int lds_floats, int shared_floats, const DevState& st, int n_envs,
-                       int n_steps, bool forward_only, int group, bool primal, bool ext, bool params, hipStream_t stream) {
-  if (params) {  // a per-env model parameter is in use (DevModel::prm_mask != 0)
+  constexpr int kSelPlain = kSelForward | kSelStep;
+  const bool helpers = st.ray_helpers && !forward_only;
+  if (params) {
     switch (group) {
-      case 8: launch_part_108(MRS_LAUNCH_PASS); break;
+      case 8: launch_part<8, kSelAll, true, true>(MRS_LAUNCH_PASS); break;
       case 16:
-        if (st.ray_helpers && !forward_only) launch_part_120(MRS_LAUNCH_PASS);
-        else launch_part_116(MRS_LAUNCH_PASS);
+        if (helpers) launch_part<16, kSelHelpers, false, true>(MRS_LAUNCH_PASS);
+        else launch_part<16, kSelPlain | kSelPrimal, true, true>(MRS_LAUNCH_PASS);
         break;
-      case 32: launch_part_132(MRS_LAUNCH_PASS); break;
-      case 64: launch_part_164(MRS_LAUNCH_PASS); break;
+      case 32: launch_part<32, kSelAll, true, true>(MRS_LAUNCH_PASS); break;
+      case 64: launch_part<64, kSelAll, true, true>(MRS_LAUNCH_PASS); break;
       default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
   }
   switch (group) {
-    case 8: launch_part_8(MRS_LAUNCH_PASS); break;
+    case 8: launch_part<8, kSelAll, true, false>(MRS_LAUNCH_PASS); break;
     case 16:
-      if (ext) launch_part_18(MRS_LAUNCH_PASS);
-      else if (st.ray_helpers && !forward_only) launch_part_19(MRS_LAUNCH_PASS);
-      else if (primal && !forward_only) launch_part_17(MRS_LAUNCH_PASS);
-      else launch_part_16(MRS_LAUNCH_PASS);
+      if (ext) launch_part<16, kSelPlain | kSelPrimal, true, false>(MRS_LAUNCH_PASS);
+      else if (helpers) launch_part<16, kSelHelpers, false, false>(MRS_LAUNCH_PASS);
+      else if (primal && !forward_only) launch_part<16, kSelPrimal, false, false>(MRS_LAUNCH_PASS);
+      else launch_part<16, kSelPlain, false, false>(MRS_LAUNCH_PASS);
       break;
-    case 32: launch_part_32(MRS_LAUNCH_PASS); break;
+    case 32: launch_part<32, kSelAll, true, false>(MRS_LAUNCH_PASS); break;
     case 64:
-      if (ext) launch_part_65(MRS_LAUNCH_PASS);
-      else launch_part_64(MRS_LAUNCH_PASS);
+      if (ext) launch_part<64, kSelAll, true, false>(MRS_LAUNCH_PASS);
+      else launch_part<64, kSelAll, false, false>(MRS_LAUNCH_PASS);
       break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
-#elif MRS_STEP_PART == 16
-void launch_part_16(MRS_LAUNCH_ARGS) { launch_g<16, kSelForward | kSelStep>(MRS_LAUNCH_PASS); }
-#elif MRS_STEP_PART == 17
-void launch_part_17(MRS_LAUNCH_ARGS) { launch_g<16, kSelPrimal>(MRS_LAUNCH_PASS); }
-#elif MRS_STEP_PART == 18
-void launch_part_18(MRS_LAUNCH_ARGS) { launch_g<16, kSelForward | kSelStep | kSelPrimal>(MRS_LAUNCH_PASS); }
-#elif MRS_STEP_PART == 19
-// G = 16 step kernels (PGS and primal) with ray helper waves, without the extended code
-void launch_part_19(MRS_LAUNCH_ARGS) { launch_g<16, kSelHelpers>(MRS_LAUNCH_PASS); }
-#elif MRS_STEP_PART == 65
-void launch_part_65(MRS_LAUNCH_ARGS) { launch_g<64>(MRS_LAUNCH_PASS); }
-#elif MRS_STEP_PART == 108
-void launch_part_108(MRS_LAUNCH_ARGS) { launch_g<8>(MRS_LAUNCH_PASS); }
-#elif MRS_STEP_PART == 116
-void launch_part_116(MRS_LAUNCH_ARGS) { launch_g<16, kSelForward | kSelStep | kSelPrimal>(MRS_LAUNCH_PASS); }
-#elif MRS_STEP_PART == 120
-void launch_part_120(MRS_LAUNCH_ARGS) { launch_g<16, kSelHelpers>(MRS_LAUNCH_PASS); }
-#elif MRS_STEP_PART == 132
-void launch_part_132(MRS_LAUNCH_ARGS) { launch_g<32>(MRS_LAUNCH_PASS); }
-#elif MRS_STEP_PART == 164
-void launch_part_164(MRS_LAUNCH_ARGS) { launch_g<64>(MRS_LAUNCH_PASS); }
-#else
-#define MRS_PART_FN2(n) launch_part_##n
-#define MRS_PART_FN(n) MRS_PART_FN2(n)
-void MRS_PART_FN(MRS_STEP_PART)(MRS_LAUNCH_ARGS) { launch_g<MRS_STEP_PART>(MRS_LAUNCH_PASS); }
-#endif
 #endif
 
 }  // namespace mrs
