@@ -303,6 +303,32 @@ int mrs_batch_render_wait(mrs_batch* b);
  * any output pointer may be NULL.  Returns ncon (which may exceed `max`) or a negative error code. */
 int mrs_batch_get_contacts(mrs_batch* b, int env, int max, int* geom, double* dist, double* pos,
                            double* frame);
+/* mj_contactForce of every contact of mrs_batch_get_contacts' list for env `env`, in its order: force
+ * [max][6] fp64 in the contact frame -- normal, tangent 1, tangent 2, then three zeros (condim 1 and 3
+ * carry no torque).  Decoded on the host from the env's contact records and the solver's row forces
+ * (the pyramid's edges as mju_decodePyramid, an elliptic block as it is, condim 1 its one row); a
+ * contact whose rows the row cap cut gives zeros.  The pyramidal decode's friction is the pair's as the
+ * kernel sees it: per-env MRS_PARAM_GEOM_FRICTION where set (max of the two geoms for automatic pairs;
+ * an explicit <contact><pair> keeps its own).  Needs no device output to be on.  Returns ncon (which
+ * may exceed `max`) or a negative error code. */
+int mrs_batch_get_contact_forces(mrs_batch* b, int env, int max, double* force);
+/* The net contact wrench per body, an output of the step: [n_envs][nbody][6] fp32.  Row b sums, in
+ * contact order, the step's contacts that involve body b: [0:3] the world-frame force on the body,
+ * [3:6] the world-frame torque about the body's centre of mass xipos_b -- MRS_FIELD_XFRC_APPLIED's
+ * layout and reference point, so writing a row back as xfrc_applied with contacts disabled reproduces
+ * the contacts' effect on that body.  Row 0 holds the wrench on the world's geoms, torque about the
+ * world origin; the rows' forces sum to zero.  Signs as mj_contactForce: the contact normal points
+ * from geom1 to geom2, the decoded force acts on geom2's body at the contact point, its negative on
+ * geom1's.  Zeros with contacts or constraints disabled; not a sensor (MRS_DSBL_SENSOR does not cover
+ * it).  The buffer does not exist until one of these two calls, which makes it zero-filled and turns
+ * the output on for all later launches; it is then written by the last step of every mrs_batch_step
+ * launch and by mrs_batch_forward, and no reset changes it.
+ * mrs_batch_contact_wrench_device_ptr: the device buffer; reads ordered on the batch stream see the last
+ * launch's values.  NULL on error, the code in mrs_last_status.
+ * mrs_batch_get_contact_wrench: host rows [n][nbody][6] fp64 of envs [env0, env0 + n); zeros until a
+ * step or forward has been launched after the output was turned on. */
+float* mrs_batch_contact_wrench_device_ptr(mrs_batch* b);
+int mrs_batch_get_contact_wrench(mrs_batch* b, double* host, int env0, int n);
 /* mjData.efc_* of env `env` after its last step / forward (the rows mj_makeConstraint built and the
  * solver's forces): up to `max` rows in mj_makeConstraint's order --
  * type [max] int32 (1 friction loss, 2 joint limit, 3 contact), J [max][nv], R [max], aref [max],
@@ -338,7 +364,8 @@ int mrs_debug_phase_cycles(double* out, int n, int reset);
  * [12] helper waves (collision, rows, rays and the integrator factor beside the dynamics), [13] the
  * integrator's factor fused into the Cholesky phase, [14] ray sweep of a static planar lidar, [15]
  * sensors evaluated on every step of a fused launch (MRS_SENSORS_EVERY_STEP=1) instead of the last
- * only.  Returns the number of values written. */
+ * only, [16] the contact-wrench output on (1; mrs_batch_contact_wrench_device_ptr) or not (0).
+ * Returns the number of values written. */
 int mrs_debug_batch_layout(const mrs_batch* b, int* out, int n);
 
 #ifdef __cplusplus

@@ -463,6 +463,32 @@ int mrs_batch_get_efc(mrs_batch* b, int env, int max, int* type, double* J, doub
   return rc == MRS_OK ? nefc : rc;
 }
 
+int mrs_batch_get_contact_forces(mrs_batch* b, int env, int max, double* force) {
+  int ncon = 0;
+  const int rc = guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    ncon = mrs::batch_get_contact_forces(b->impl, env, max, force);
+  });
+  return rc == MRS_OK ? ncon : rc;
+}
+
+float* mrs_batch_contact_wrench_device_ptr(mrs_batch* b) {
+  // (the buffer is made on first use, which can fail: NULL then, the code in mrs_last_status)
+  float* p = nullptr;
+  guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    p = mrs::batch_contact_wrench_device_ptr(b->impl);
+  });
+  return p;
+}
+
+int mrs_batch_get_contact_wrench(mrs_batch* b, double* host, int env0, int n) {
+  return guarded([&] {
+    if (!b || !host) throw std::invalid_argument("null argument");
+    mrs::batch_get_contact_wrench(b->impl, host, env0, n);
+  });
+}
+
 int mrs_batch_get_field_device(mrs_batch* b, int field, float* d_out, int env0, int n) {
   return guarded([&] {
     if (!b || !d_out) throw std::invalid_argument("null argument");

@@ -59,6 +59,12 @@ void batch_render_async(BatchImpl* b, int cam, int env0, int n, float* d_out, un
 void batch_render_wait(BatchImpl* b);
 int batch_get_contacts(BatchImpl* b, int env, int max, int* geom, double* dist, double* pos, double* frame);
 int batch_get_efc(BatchImpl* b, int env, int max, int* type, double* J, double* R, double* aref, double* force);
+// mj_contactForce per contact of batch_get_contacts' list ([max][6], contact frame; returns ncon), and the
+// net contact wrench per body [n_envs][nbody][6]: its device buffer, made on first use, which turns the
+// output on for every later launch, and host rows [n][nbody][6]
+int batch_get_contact_forces(BatchImpl* b, int env, int max, double* force);
+float* batch_contact_wrench_device_ptr(BatchImpl* b);
+void batch_get_contact_wrench(BatchImpl* b, double* host, int env0, int n);
 void batch_get_field_device(BatchImpl* b, int field, float* d_out, int env0, int n);
 void batch_sync(BatchImpl* b);
 double batch_last_kernel_ms(BatchImpl* b, int kind);

@@ -1006,6 +1006,8 @@ struct BatchImpl {
   int timing = 2;
   std::vector<float> staging;
   std::vector<int> pair_g1, pair_g2;  // host copy of the static collision pairs (contact export)
+  std::vector<int> pair_dim;          // their condim and sliding friction (batch_get_contact_forces)
+  std::vector<float> pair_mu;
   // camera pipeline (batch_render_async): pose snapshot + side stream, as the reference's rendering
   // thread renders its mjv_copyData snapshot while PhysicsLoop steps on (src/mujoco_cameras.cpp:204-215)
   hipStream_t rstream = nullptr;
@@ -1293,6 +1295,9 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
   d.npair = static_cast<int>(pg1.size());
   d.npair_explicit = static_cast<int>(m.expair_geom1.size());
   b.pair_g1 = pg1;
+  b.pair_dim = pdim;
+  b.pair_mu.resize(pg1.size());
+  for (size_t q = 0; q < pg1.size(); ++q) b.pair_mu[q] = pfric[3 * q];
   // active equality constraints (rows first in the solver order, as mj_makeConstraint)
   std::vector<int> eq_t, eq_o1, eq_o2;
   std::vector<double> eq_sr, eq_si, eq_dat;
@@ -2300,12 +2305,13 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
 // DevModel: the table points at that slot and keeps no copy), its elements per env, their type and
 // when the array is made -- and creation, the row copies and the accessors below all go by it.
 // Ids: the MRS_FIELD_* values, then
-enum { kArrAct = MRS_FIELD_COUNT, kArrMocapPos, kArrMocapQuat, kArrParam0, kArrInertial = kArrParam0 + MRS_PARAM_COUNT, kArrCount };
+enum { kArrAct = MRS_FIELD_COUNT, kArrMocapPos, kArrMocapQuat, kArrParam0, kArrInertial = kArrParam0 + MRS_PARAM_COUNT,
+       kArrContactWrench, kArrCount };
 
 struct EnvArray {
   enum Type { F32, I32, F64 } type;
   // AT_CREATE: with the batch, a buffer even when dim == 0; IF_DIM: with the batch, null when dim == 0;
-  // ON_USE: null until first used (ensure_xfrc, ensure_param, ensure_inertial)
+  // ON_USE: null until first used (ensure_xfrc, ensure_param, ensure_inertial, ensure_contact_wrench)
   enum Made { AT_CREATE, IF_DIM, ON_USE } made;
   int dim;     // elements per env; -1: no such array
   void* ptr;   // the array as its slot holds it now (null: not made)
@@ -2348,6 +2354,7 @@ EnvArray env_array(BatchImpl& b, int id) {
     case kArrParam0 + MRS_PARAM_DOF_DAMPING: return env_array_at(d.prm_damp, m.nv, EnvArray::ON_USE);
     case kArrParam0 + MRS_PARAM_GEOM_FRICTION: return env_array_at(d.prm_fric, m.ngeom, EnvArray::ON_USE);
     case kArrInertial: return env_array_at(d.prm_inr, inertial_layout(m).dim, EnvArray::ON_USE);
+    case kArrContactWrench: return env_array_at(d.cfrc_contact, 6 * m.nbody, EnvArray::ON_USE);
   }
   return {EnvArray::F32, EnvArray::ON_USE, -1, nullptr, nullptr};
 }
@@ -2497,6 +2504,21 @@ float* ensure_inertial(BatchImpl& b) {
   return p;
 }
 
+// the net contact wrench per body [n][nbody][6] (an output; DevModel::cfrc_contact), made and zero-filled
+// when it is first asked for; from then on every launch's last forward pass writes it (step.hip
+// contact_wrench_out).  Like ensure_xfrc: the earlier launches have finished before the model block
+// changes.  No reset touches it, as none touches qacc or sensordata
+float* ensure_contact_wrench(BatchImpl& b) {
+  const EnvArray a = env_array(b, kArrContactWrench);
+  if (a.ptr) return static_cast<float*>(a.ptr);
+  HIP_CHECK(hipSetDevice(b.device));
+  float* p = static_cast<float*>(dalloc(b, static_cast<size_t>(b.n) * a.dim * sizeof(float)));
+  HIP_CHECK(hipStreamSynchronize(b.stream));
+  a.bind(p);
+  HIP_CHECK(hipMemcpy(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice));
+  return p;
+}
+
 // the model's start states as the masked reset reads them: b.start (start_rows.h) in one device table
 void upload_start_table(BatchImpl& b) {
   auto put = [&](const void* src, size_t bytes) {
@@ -2629,11 +2651,12 @@ void batch_free(BatchImpl* b) {
 int batch_num_envs(const BatchImpl* b) { return b->n; }
 
 int batch_layout(const BatchImpl* b, int* out, int n) {
-  const int v[16] = {b->group, b->dm.L.total, b->dm.S.total, b->dm.blocked, b->dm.pipe_w, b->dm.max_efc,
+  const int v[17] = {b->group, b->dm.L.total, b->dm.S.total, b->dm.blocked, b->dm.pipe_w, b->dm.max_efc,
                      b->dm.max_con, b->dm.ntree, b->dm.shr_total, b->dm.rf_common, b->g16_one_wg,
-                     b->group == 16 ? b->wpb16 : 0, b->helpers, b->dm.fuse_ih, b->dm.rf_sweep, b->dm.sens_every};
+                     b->group == 16 ? b->wpb16 : 0, b->helpers, b->dm.fuse_ih, b->dm.rf_sweep, b->dm.sens_every,
+                     b->dm.cfrc_contact ? 1 : 0};
   int k = 0;
-  for (; k < n && k < 16; ++k) out[k] = v[k];
+  for (; k < n && k < 17; ++k) out[k] = v[k];
   return k;
 }
 
@@ -3166,6 +3189,76 @@ int batch_get_contacts(BatchImpl* b, int env, int max, int* geom, double* dist, 
     if (frame) for (int i = 0; i < 9; ++i) frame[9 * c + i] = r[5 + i];
   }
   return ncon;
+}
+
+// mj_contactForce of every contact of batch_get_contacts' list, in its order: [max][6] in the contact
+// frame (normal, tangent 1, tangent 2, then the torques, zero at condim 1 and 3), decoded on the host
+// from the env's contact records and row forces (efc_f at the record's first row, rec[14]) as step.hip
+// rne_post decodes them; a contact whose rows the cap cut gives zeros.  The pyramid's friction is the
+// pair's as the kernel sees it (pair_mu): per-env geom friction where the parameter is set.  Returns ncon
+int batch_get_contact_forces(BatchImpl* b, int env, int max, double* force) {
+  if (env < 0 || env >= b->n) throw std::invalid_argument("env out of bounds");
+  if (max < 0) throw std::invalid_argument("negative capacity");
+  if (max > 0 && !force) throw std::invalid_argument("null force buffer");
+  HIP_CHECK(hipSetDevice(b->device));
+  int ncon = 0;
+  HIP_CHECK(hipMemcpyAsync(&ncon, b->st.ncon + env, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  HIP_CHECK(hipStreamSynchronize(b->stream));
+  const int n = std::min(ncon, max);
+  if (n <= 0) return ncon;
+  const Model& m = *b->model;
+  const ScratchLayout& S = b->S;
+  const float* base = b->st.scratch + static_cast<size_t>(env) * S.total;
+  const int ne = std::max(1, b->dm.max_efc);
+  std::vector<float> rec(static_cast<size_t>(n) * kConRec), f(ne), fric;
+  HIP_CHECK(hipMemcpyAsync(rec.data(), base + S.con, rec.size() * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+  HIP_CHECK(hipMemcpyAsync(f.data(), base + S.efc_f, f.size() * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+  if (b->dm.prm_fric) {
+    fric.resize(m.ngeom);
+    HIP_CHECK(hipMemcpyAsync(fric.data(), b->dm.prm_fric + static_cast<size_t>(env) * m.ngeom, fric.size() * sizeof(float),
+                             hipMemcpyDeviceToHost, b->stream));
+  }
+  HIP_CHECK(hipStreamSynchronize(b->stream));
+  const bool elliptic = m.cone == MRS_CONE_ELLIPTIC;
+  for (int c = 0; c < n; ++c) {
+    const float* r = &rec[static_cast<size_t>(c) * kConRec];
+    double* out = force + 6 * static_cast<size_t>(c);
+    std::fill(out, out + 6, 0.0);
+    int p, r0;
+    std::memcpy(&p, r, sizeof(int));
+    std::memcpy(&r0, r + 14, sizeof(int));
+    if (p < 0 || p >= static_cast<int>(b->pair_g1.size())) throw DeviceError("corrupt contact record");
+    if (r0 < 0) continue;
+    const int rows = b->pair_dim[p] == 1 ? 1 : (elliptic ? 3 : 4);
+    if (r0 + rows > ne) throw DeviceError("corrupt contact record");
+    if (b->pair_dim[p] == 1) {
+      out[0] = f[r0];
+    } else if (elliptic) {
+      for (int i = 0; i < 3; ++i) out[i] = f[r0 + i];
+    } else {
+      float mu = b->pair_mu[p];
+      if (!fric.empty() && p >= b->dm.npair_explicit) mu = std::max(fric[b->pair_g1[p]], fric[b->pair_g2[p]]);
+      // (in fp32 and in the kernel's order of operations: the same value as its decode)
+      float lf[3] = {0, 0, 0};
+      for (int k = 0; k < 2; ++k) {
+        const float fp = f[r0 + 2 * k], fm = f[r0 + 2 * k + 1];
+        lf[0] += fp + fm;
+        lf[k + 1] = (fp - fm) * mu;
+      }
+      for (int i = 0; i < 3; ++i) out[i] = lf[i];
+    }
+  }
+  return ncon;
+}
+
+// the net contact wrench per body: the device buffer [n_envs][nbody][6] (made on first use, which turns
+// the output on for every later launch), and host rows [n][nbody][6] of it
+float* batch_contact_wrench_device_ptr(BatchImpl* b) { return ensure_contact_wrench(*b); }
+
+void batch_get_contact_wrench(BatchImpl* b, double* host, int env0, int n) {
+  check_env_range(*b, env0, n);
+  ensure_contact_wrench(*b);
+  rows_to_host(*b, env0, n, {{env_array(*b, kArrContactWrench), host}});
 }
 
 // fp32 field rows [env0, env0 + n) into a caller device buffer [n][dim], ordered on the batch stream

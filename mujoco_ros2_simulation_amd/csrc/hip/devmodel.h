@@ -263,9 +263,16 @@ struct DevModel {
   // prm_mask is set with it).  [n_envs][inr_dim] fp32, one row per env (start_rows.h InertialLayout):
   // mass [nbody], inertia [3 nbody], armature [nv], body_subtreemass [nbody], dof_invweight0 [nv],
   // body_invweight0 [2 nbody], the friction-loss rows' R [nfric], pgs_scale [1].  The lane group's row
-  // is the one xfrc_row uses.  Kept last: the fields above keep their offsets
+  // is the one xfrc_row uses.  Kept after the fields above, which keep their offsets
   const float* prm_inr;
   int inr_dim;
+  // the net contact wrench per body, an output: [n_envs][nbody][6] fp32, row b the
+  // world-frame force, then the torque about xipos_b, of the step's contacts on body b (row 0: on the
+  // world's geoms, about the origin).  Null until the output is first asked for (batch.hip
+  // ensure_contact_wrench); from then on every forward pass that evaluates the sensors writes it
+  // (step.hip contact_wrench_out, behind the wave-uniform test of this pointer).  The lane group's row
+  // is the one xfrc_row uses.  Kept last: the fields above keep their offsets
+  float* cfrc_contact;
 };
 constexpr int kRayBlock = 128;
 // bits of DevModel::prm_mask (1 << MRS_PARAM_*)

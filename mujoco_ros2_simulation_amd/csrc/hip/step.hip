@@ -6726,6 +6726,59 @@ __device__ MRS_PHASE void rne_post(ENV_PARAMS, int ncon) {
   wsync();
 }
 
+// the net contact wrench per body (batches that asked for it only: DevModel::cfrc_contact non-null, a
+// wave-uniform test at the call): row b of the env's [nbody][6] output is the sum, in
+// contact order, over this step's contacts that involve body b of the world-frame force on the body
+// and its torque about xipos_b -- xfrc_applied's layout and reference point; row 0 the wrench on the
+// world's geoms about the origin.  Sign and decode are rne_post's: F = frame' lf acts on geom2's body
+// at pos, -F on geom1's; a contact whose rows the cap cut gives nothing.  One lane per body, no
+// atomics.  The env row is the one xfrc_row uses; a group that writes nothing back (a mirror, or one
+// past n_envs: step_kernel points its sensordata at the scratch sink) stores nothing.  Needs the row
+// forces (efc_f) and the contact records of this step
+template <int G>
+__device__ __attribute__((noinline)) void contact_wrench_out(ENV_PARAMS, int ncon, const gfloat* sensordata) {
+  ENV_UNPACK;
+  const int row = __float_as_int(scr[S.xfrc]);
+  if (row < 0 || sensordata == scr + S.sens) return;
+  gfloat* out = (gfloat*)m.cfrc_contact + (size_t)row * 6 * m.nbody;
+  const gfloat* ff = scr + S.efc_f;
+  #pragma unroll 1
+  for (int b = lane; b < m.nbody; b += G) {
+    float w[6] = {0, 0, 0, 0, 0, 0};
+    float c3[3] = {0, 0, 0};
+    if (b != 0) { c3[0] = s[L.xipos + 3 * b]; c3[1] = s[L.xipos + 3 * b + 1]; c3[2] = s[L.xipos + 3 * b + 2]; }
+    #pragma unroll 1
+    for (int c = 0; c < ncon; ++c) {
+      const gfloat* rec = scr + S.con + kConRec * c;
+      const int p = __float_as_int(rec[0]);
+      const int b1 = m.geom_bodyid[m.pair_g1[p]], b2 = m.geom_bodyid[m.pair_g2[p]];
+      const int r0 = __float_as_int(rec[14]);
+      if ((b != b1 && b != b2) || r0 < 0) continue;
+      // contact-frame force (mju_decodePyramid), then world: frame' lf
+      float lf[3] = {0, 0, 0};
+      if (m.pair_dim[p] == 1) {
+        lf[0] = ff[r0];
+      } else if (m.cone == MRS_CONE_ELLIPTIC) {
+        for (int i = 0; i < 3; ++i) lf[i] = ff[r0 + i];  // (normal, tangent 1, tangent 2)
+      } else {
+        for (int k = 0; k < 2; ++k) {
+          const float fp = ff[r0 + 2 * k], fm = ff[r0 + 2 * k + 1];
+          lf[0] += fp + fm;
+          lf[k + 1] = (fp - fm) * pair_mu(m, scr, p);
+        }
+      }
+      float F[3];
+      for (int i = 0; i < 3; ++i) F[i] = rec[5 + i] * lf[0] + rec[8 + i] * lf[1] + rec[11 + i] * lf[2];
+      const float d[3] = {rec[2] - c3[0], rec[3] - c3[1], rec[4] - c3[2]};
+      float tq[3];
+      cross3(tq, d, F);
+      const float sg = b == b2 ? 1.0f : -1.0f;  // + on geom2's body, - on geom1's
+      for (int i = 0; i < 3; ++i) { w[i] += sg * F[i]; w[3 + i] += sg * tq[i]; }
+    }
+    for (int i = 0; i < 6; ++i) out[6 * b + i] = w[i];
+  }
+}
+
 // rays per lane per pass over the geoms: 4 with lane groups (measured C3: 1.59 ms per launch vs
 // 1.98 at 1, 1.71 at 2), 2 at one env per wave (64-VGPR budget: 2.15 ms vs 2.38 at 1, 2.95 at 4)
 template <int G>
@@ -7686,6 +7739,9 @@ __device__ MRS_PHASE int forward(ENV_PARAMS, gfloat* sensordata, bool sens PH_AC
     if (m.acc_sens && !(m.disableflags & MRS_DSBL_SENSOR)) { [[clang::noinline]] rne_post<G>(ENV_ARGS, ncon); }
     if (!(m.diag_skip & 1)) MRS_CALL(G, sensors<G>(ENV_ARGS, sensordata, !helper));
     if (m.nsens_more && !(m.disableflags & MRS_DSBL_SENSOR)) { [[clang::noinline]] sensors_more<G>(ENV_ARGS, sensordata, ncon); }
+    // the net contact wrench per body, an output and not a sensor (no disable flag covers it); out of
+    // line, so a batch that never asked for it pays this scalar test alone
+    if (m.cfrc_contact) { [[clang::noinline]] contact_wrench_out<G>(ENV_ARGS, (m.diag_skip & 4) ? 0 : ncon, sensordata); }
   }
   PH_END(ph_acc, PH_SENS);
   return ncon;
@@ -8091,8 +8147,9 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
     }
   }
   // xfrc_applied or a per-env model parameter in use: the group's row of them for the phases (xfrc_row,
-  // prm_at) -- a mirror group reads its primary's env, a group past n_envs none
-  if ((st.xfrc_applied || (kPrm && m.prm_mask)) && lane == 0 && !is_helper) scr[m.S.xfrc] = __int_as_float(env < n_envs ? env : -1);
+  // prm_at) -- a mirror group reads its primary's env, a group past n_envs none; the contact-wrench
+  // output's row is the same one (contact_wrench_out)
+  if ((st.xfrc_applied || (kPrm && m.prm_mask) || m.cfrc_contact) && lane == 0 && !is_helper) scr[m.S.xfrc] = __int_as_float(env < n_envs ? env : -1);
   if constexpr (G == 64) {
     #pragma unroll 1
     for (int t = lane; t < m.ntree; t += G) {

@@ -271,6 +271,11 @@ def lib() -> C.CDLL:
                                              C.c_void_p]
         L.mrs_batch_get_efc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]
+        if hasattr(L, "mrs_batch_get_contact_wrench"):  # (an A/B library named by MRS_LIB may predate them)
+            L.mrs_batch_get_contact_forces.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+            L.mrs_batch_contact_wrench_device_ptr.restype = C.c_void_p
+            L.mrs_batch_contact_wrench_device_ptr.argtypes = [C.c_void_p]
+            L.mrs_batch_get_contact_wrench.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.mrs_batch_get_field_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.mrs_batch_last_kernel_ms.restype = C.c_double
         L.mrs_batch_last_kernel_ms.argtypes = [C.c_void_p, C.c_int]
@@ -412,6 +417,9 @@ _FIELD_DIM = {
 LAYOUT_KEYS = ["group", "lds_floats", "scratch_floats", "blocked", "pipe_w", "max_efc", "max_con", "ntree",
                "shared_floats", "rf_common", "one_workgroup_per_cu", "waves_per_workgroup", "helper_waves",
                "fused_integrator_factor", "ray_sweep", "sensors_every_step"]
+# the values after them: the batch's optional outputs, 1 once asked for (contact_wrench: the net contact
+# wrench per body, Batch.contact_wrench)
+LAYOUT_OUTPUT_KEYS = ["contact_wrench"]
 
 
 class Batch:
@@ -609,9 +617,9 @@ class Batch:
     def layout(self) -> dict:
         """kernel configuration of this batch (diagnostics): group width, LDS and scratch floats per
         env, blocked mode, pipe width, row and contact capacity, kinematic trees"""
-        out = np.zeros(len(LAYOUT_KEYS), dtype=np.int32)
-        k = lib().mrs_debug_batch_layout(self._h, out.ctypes.data, len(LAYOUT_KEYS))
-        keys = LAYOUT_KEYS
+        keys = LAYOUT_KEYS + LAYOUT_OUTPUT_KEYS
+        out = np.zeros(len(keys), dtype=np.int32)
+        k = lib().mrs_debug_batch_layout(self._h, out.ctypes.data, len(keys))
         return dict(zip(keys[:k], out[:k].tolist()))
 
     def step(self, n_steps: int = 1) -> None:
@@ -691,6 +699,30 @@ class Batch:
             _check(n)
         n = min(n, max_n)
         return {"type": t[:n], "J": J[:n, :nv], "R": R[:n], "aref": a[:n], "force": f[:n]}
+
+    def contact_forces(self, env: int = 0, max_n: int = 256) -> np.ndarray:
+        """mj_contactForce of every contact of `contacts(env)`, in its order: [ncon, 6] in the contact
+        frame (normal, tangent 1, tangent 2, then three zeros); a contact without rows gives zeros"""
+        f = np.zeros((max_n, 6))
+        n = lib().mrs_batch_get_contact_forces(self._h, env, max_n, f.ctypes.data)
+        if n < 0:
+            _check(n)
+        return f[:min(n, max_n)]
+
+    def contact_wrench(self, env0: int = 0, n: int | None = None) -> np.ndarray:
+        """the net contact wrench per body [n, nbody, 6] of the last launch: world-frame force, then
+        torque about the body's centre of mass (xfrc_applied's layout; row 0: on the world's geoms, about
+        the origin).  The first call (or contact_wrench_device_ptr) turns the output on: zeros until a
+        step or forward has been launched after it"""
+        return self._get_rows(lib().mrs_batch_get_contact_wrench, (), [(self.model.nbody, 6)], env0, n)[0]
+
+    def contact_wrench_device_ptr(self) -> int:
+        """the net contact wrenches on the device, fp32 [n_envs, nbody, 6], ordered on the batch stream;
+        turns the output on for all later launches"""
+        p = lib().mrs_batch_contact_wrench_device_ptr(self._h)
+        if not p:
+            raise MrsError(lib().mrs_last_status() or -3, lib().mrs_last_error().decode())
+        return p
 
     def get_device(self, field: int, dptr: int, env0: int = 0, n: int | None = None) -> None:
         """fp32 rows of `field` into a device buffer [n, dim], asynchronous on the batch stream"""
