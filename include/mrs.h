@@ -329,6 +329,49 @@ int mrs_batch_get_contact_forces(mrs_batch* b, int env, int max, double* force);
  * step or forward has been launched after the output was turned on. */
 float* mrs_batch_contact_wrench_device_ptr(mrs_batch* b);
 int mrs_batch_get_contact_wrench(mrs_batch* b, double* host, int env0, int n);
+/* The dynamics outputs: what model-based control is built from (gravity compensation tau = qfrc_bias,
+ * computed torque tau = M qdd + qfrc_bias, Cartesian impedance tau = J' F), per env, on the device.
+ * (The constants are MRS_DYNOUT_*, not MRS_DYN_*: that prefix is the actuator dyntype's, mrs_model.h.) */
+enum {
+  MRS_DYNOUT_QFRC_BIAS = 0,   /* [nv]          mjData.qfrc_bias (Coriolis, centrifugal, gravity) */
+  MRS_DYNOUT_MASS_MATRIX = 1, /* [nv][nv]      mj_fullM: dense, symmetric, both triangles written, zeros between trees */
+  MRS_DYNOUT_SITE_JAC = 2,    /* [nsel][6][nv] mj_jacSite: rows 0..2 jacp, rows 3..5 jacr, world frame */
+  MRS_DYNOUT_SITE_POSE = 3,   /* [nsel][12]    mjData.site_xpos [3] then site_xmat [9] row-major */
+  MRS_DYNOUT_COUNT = 4
+};
+#define MRS_MAX_JAC_SITES 16
+/* Each output is a device buffer [n_envs][dim] fp32 that does not exist until it is first asked for
+ * (mrs_batch_dyn_device_ptr or mrs_batch_get_dyn with that `which`): that call makes it zero-filled and
+ * turns the output on for all later launches; a batch with no output on launches the kernels it
+ * launched before, which hold none of this code.  They are outputs, not sensors: MRS_DSBL_SENSOR does not cover them.
+ *
+ * Which state the values belong to: the forward pass whose sensors are in sensordata.  After
+ * mrs_batch_step(b, n) that is the last step's forward pass, i.e. the state BEFORE that step's
+ * integration -- what mjData holds after mj_step (under RK4 the step's first stage; under
+ * MRS_SENSORS_EVERY_STEP=1 the same pass).  After mrs_batch_forward it is the current qpos / qvel.  A
+ * controller that wants values consistent with the qpos it reads calls mrs_batch_forward.  No reset
+ * writes the buffers (as none writes qacc); the re-run of a step after a NaN auto-reset writes them
+ * like any other forward pass.
+ *
+ * The mass matrix and qfrc_bias are the env's own: copies of what the env's step used, so they carry
+ * per-env masses, inertias and armatures (mrs_batch_set_inertial) -- which a host-side model cannot
+ * give.  qfrc_bias follows MRS_DSBL_GRAVITY as the step's own does.
+ *
+ * mrs_batch_set_jac_sites: the sites (ids from mrs_name2id(MRS_OBJ_SITE), n in [0, MRS_MAX_JAC_SITES])
+ * that SITE_JAC and SITE_POSE cover, in the given order; nsel = n.  With no selection nsel = 0: the two
+ * dimensions are 0, their device pointer is NULL (mrs_last_status MRS_OK) and mrs_batch_get_dyn copies
+ * nothing.  Changing the selection synchronises, frees the two buffers and remakes those that have
+ * been asked for zero-filled (device pointers obtained before are invalid).  MRS_ERR_INVALID for an id outside
+ * [0, nsite), a duplicate, or n > MRS_MAX_JAC_SITES; a rejected call changes nothing.
+ * mrs_batch_dyn_dim: floats per env of the output (negative error code for an unknown `which`).
+ * mrs_batch_dyn_device_ptr: the device buffer; reads ordered on the batch stream see the last launch's
+ * values.  NULL on error, the code in mrs_last_status.
+ * mrs_batch_get_dyn: host rows [n][dim] fp64 of envs [env0, env0 + n); zeros until a step or forward
+ * has been launched after the output was turned on. */
+int mrs_batch_set_jac_sites(mrs_batch* b, const int* site_ids, int n);
+int mrs_batch_dyn_dim(const mrs_batch* b, int which);
+float* mrs_batch_dyn_device_ptr(mrs_batch* b, int which);
+int mrs_batch_get_dyn(mrs_batch* b, int which, double* host, int env0, int n);
 /* mjData.efc_* of env `env` after its last step / forward (the rows mj_makeConstraint built and the
  * solver's forces): up to `max` rows in mj_makeConstraint's order --
  * type [max] int32 (1 friction loss, 2 joint limit, 3 contact), J [max][nv], R [max], aref [max],
@@ -364,7 +407,9 @@ int mrs_debug_phase_cycles(double* out, int n, int reset);
  * [12] helper waves (collision, rows, rays and the integrator factor beside the dynamics), [13] the
  * integrator's factor fused into the Cholesky phase, [14] ray sweep of a static planar lidar, [15]
  * sensors evaluated on every step of a fused launch (MRS_SENSORS_EVERY_STEP=1) instead of the last
- * only, [16] the contact-wrench output on (1; mrs_batch_contact_wrench_device_ptr) or not (0).
+ * only, [16] the contact-wrench output on (1; mrs_batch_contact_wrench_device_ptr) or not (0), [17]
+ * the dynamics outputs that are on, a bit mask (1 << MRS_DYNOUT_*; a site output's bit only while sites
+ * are selected).
  * Returns the number of values written. */
 int mrs_debug_batch_layout(const mrs_batch* b, int* out, int n);
 

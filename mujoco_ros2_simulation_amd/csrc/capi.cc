@@ -489,6 +489,39 @@ int mrs_batch_get_contact_wrench(mrs_batch* b, double* host, int env0, int n) {
   });
 }
 
+int mrs_batch_set_jac_sites(mrs_batch* b, const int* site_ids, int n) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_set_jac_sites(b->impl, site_ids, n);
+  });
+}
+
+int mrs_batch_dyn_dim(const mrs_batch* b, int which) {
+  int dim = 0;
+  const int rc = guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    dim = mrs::batch_dyn_dim(b->impl, which);
+  });
+  return rc == MRS_OK ? dim : rc;
+}
+
+float* mrs_batch_dyn_device_ptr(mrs_batch* b, int which) {
+  // (NULL with MRS_OK in mrs_last_status: a site output with no site selected; NULL otherwise: the error)
+  float* p = nullptr;
+  guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    p = mrs::batch_dyn_device_ptr(b->impl, which);
+  });
+  return p;
+}
+
+int mrs_batch_get_dyn(mrs_batch* b, int which, double* host, int env0, int n) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_get_dyn(b->impl, which, host, env0, n);
+  });
+}
+
 int mrs_batch_get_field_device(mrs_batch* b, int field, float* d_out, int env0, int n) {
   return guarded([&] {
     if (!b || !d_out) throw std::invalid_argument("null argument");

@@ -65,6 +65,12 @@ int batch_get_efc(BatchImpl* b, int env, int max, int* type, double* J, double* 
 int batch_get_contact_forces(BatchImpl* b, int env, int max, double* force);
 float* batch_contact_wrench_device_ptr(BatchImpl* b);
 void batch_get_contact_wrench(BatchImpl* b, double* host, int env0, int n);
+// the dynamics outputs (mrs.h MRS_DYNOUT_*): the site selection, floats per env, the device buffer (made on
+// first use, which turns the output on for every later launch) and host rows [n][dim]
+void batch_set_jac_sites(BatchImpl* b, const int* site_ids, int n);
+int batch_dyn_dim(const BatchImpl* b, int which);
+float* batch_dyn_device_ptr(BatchImpl* b, int which);
+void batch_get_dyn(BatchImpl* b, int which, double* host, int env0, int n);
 void batch_get_field_device(BatchImpl* b, int field, float* d_out, int env0, int n);
 void batch_sync(BatchImpl* b);
 double batch_last_kernel_ms(BatchImpl* b, int kind);

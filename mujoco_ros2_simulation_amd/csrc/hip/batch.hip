@@ -30,7 +30,8 @@
 namespace mrs {
 
 hipError_t launch_step(const DevModel* d_model, int lds_floats, int shared_floats, const DevState& st, int n_envs,
-                       int n_steps, bool forward_only, int group, bool primal, bool ext, bool params, hipStream_t stream);
+                       int n_steps, bool forward_only, int group, bool primal, bool ext, bool params, bool dyn,
+                       hipStream_t stream);
 
 namespace {
 
@@ -1008,6 +1009,7 @@ struct BatchImpl {
   std::vector<int> pair_g1, pair_g2;  // host copy of the static collision pairs (contact export)
   std::vector<int> pair_dim;          // their condim and sliding friction (batch_get_contact_forces)
   std::vector<float> pair_mu;
+  int dyn_asked = 0;  // the dynamics outputs asked for so far (1 << MRS_DYNOUT_*; ensure_dyn, batch_set_jac_sites)
   // camera pipeline (batch_render_async): pose snapshot + side stream, as the reference's rendering
   // thread renders its mjv_copyData snapshot while PhysicsLoop steps on (src/mujoco_cameras.cpp:204-215)
   hipStream_t rstream = nullptr;
@@ -2306,12 +2308,17 @@ void build_devmodel(BatchImpl& b, int max_con_req) {
 // when the array is made -- and creation, the row copies and the accessors below all go by it.
 // Ids: the MRS_FIELD_* values, then
 enum { kArrAct = MRS_FIELD_COUNT, kArrMocapPos, kArrMocapQuat, kArrParam0, kArrInertial = kArrParam0 + MRS_PARAM_COUNT,
-       kArrContactWrench, kArrCount };
+       kArrContactWrench, kArrDyn0, kArrCount = kArrDyn0 + MRS_DYNOUT_COUNT };
+static_assert(MRS_DYNOUT_COUNT == 4 && MRS_MAX_JAC_SITES == 16 && kDynBias == 1 << MRS_DYNOUT_QFRC_BIAS &&
+                  kDynM == 1 << MRS_DYNOUT_MASS_MATRIX && kDynJac == 1 << MRS_DYNOUT_SITE_JAC &&
+                  kDynPose == 1 << MRS_DYNOUT_SITE_POSE,
+              "DevModel::dyn_out / dyn_site / dyn_mask follow mrs.h");
 
 struct EnvArray {
   enum Type { F32, I32, F64 } type;
   // AT_CREATE: with the batch, a buffer even when dim == 0; IF_DIM: with the batch, null when dim == 0;
-  // ON_USE: null until first used (ensure_xfrc, ensure_param, ensure_inertial, ensure_contact_wrench)
+  // ON_USE: null until first used (ensure_xfrc, ensure_param, ensure_inertial, ensure_contact_wrench,
+  // ensure_dyn)
   enum Made { AT_CREATE, IF_DIM, ON_USE } made;
   int dim;     // elements per env; -1: no such array
   void* ptr;   // the array as its slot holds it now (null: not made)
@@ -2326,6 +2333,18 @@ EnvArray env_array_at(T*& slot, int dim, EnvArray::Made made = EnvArray::AT_CREA
   using U = typename std::remove_const<T>::type;
   return {std::is_same<U, double>::value ? EnvArray::F64 : std::is_same<U, int>::value ? EnvArray::I32 : EnvArray::F32,
           made, dim, const_cast<U*>(slot), &slot};
+}
+
+// floats per env of dynamics output `which` (MRS_DYNOUT_*); the site outputs' follow the selection
+int dyn_dim(const BatchImpl& b, int which) {
+  const Model& m = *b.model;
+  switch (which) {
+    case MRS_DYNOUT_QFRC_BIAS: return m.nv;
+    case MRS_DYNOUT_MASS_MATRIX: return m.nv * m.nv;
+    case MRS_DYNOUT_SITE_JAC: return b.dm.dyn_nsel * 6 * m.nv;
+    case MRS_DYNOUT_SITE_POSE: return b.dm.dyn_nsel * 12;
+  }
+  throw std::invalid_argument("unknown dynamics output");
 }
 
 EnvArray env_array(BatchImpl& b, int id) {
@@ -2355,6 +2374,10 @@ EnvArray env_array(BatchImpl& b, int id) {
     case kArrParam0 + MRS_PARAM_GEOM_FRICTION: return env_array_at(d.prm_fric, m.ngeom, EnvArray::ON_USE);
     case kArrInertial: return env_array_at(d.prm_inr, inertial_layout(m).dim, EnvArray::ON_USE);
     case kArrContactWrench: return env_array_at(d.cfrc_contact, 6 * m.nbody, EnvArray::ON_USE);
+    case kArrDyn0 + MRS_DYNOUT_QFRC_BIAS:
+    case kArrDyn0 + MRS_DYNOUT_MASS_MATRIX:
+    case kArrDyn0 + MRS_DYNOUT_SITE_JAC:
+    case kArrDyn0 + MRS_DYNOUT_SITE_POSE: return env_array_at(d.dyn_out[id - kArrDyn0], dyn_dim(b, id - kArrDyn0), EnvArray::ON_USE);
   }
   return {EnvArray::F32, EnvArray::ON_USE, -1, nullptr, nullptr};
 }
@@ -2519,6 +2542,24 @@ float* ensure_contact_wrench(BatchImpl& b) {
   return p;
 }
 
+// dynamics output `which` [n][dim] (DevModel::dyn_out, its bit of dyn_mask), made and zero-filled when it is
+// first asked for; from then on every launch's last forward pass writes it (step.hip dyn_outputs).  Like
+// ensure_contact_wrench.  A site output with no site selected has no buffer (null) but counts as asked for:
+// batch_set_jac_sites makes it with the selection
+float* ensure_dyn(BatchImpl& b, int which) {
+  const int dim = dyn_dim(b, which);  // (throws for an unknown output)
+  const EnvArray a = env_array(b, kArrDyn0 + which);
+  b.dyn_asked |= 1 << which;
+  if (a.ptr || dim == 0) return static_cast<float*>(a.ptr);
+  HIP_CHECK(hipSetDevice(b.device));
+  float* p = static_cast<float*>(dalloc(b, static_cast<size_t>(b.n) * dim * sizeof(float)));
+  HIP_CHECK(hipStreamSynchronize(b.stream));
+  a.bind(p);
+  b.dm.dyn_mask |= 1 << which;
+  HIP_CHECK(hipMemcpy(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice));
+  return p;
+}
+
 // the model's start states as the masked reset reads them: b.start (start_rows.h) in one device table
 void upload_start_table(BatchImpl& b) {
   auto put = [&](const void* src, size_t bytes) {
@@ -2608,7 +2649,7 @@ BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_cont
       prod.rf_sweep = 0;  // (the producer pass is a block pass over the static geoms)
       DevModel* d_prod = static_cast<DevModel*>(dalloc(*b, sizeof(DevModel)));
       HIP_CHECK(hipMemcpyAsync(d_prod, &prod, sizeof(DevModel), hipMemcpyHostToDevice, b->stream));
-      HIP_CHECK(launch_step(d_prod, b->L.total, b->dm.shr_total, b->st, 1, 1, true, b->group, false, b->ext, false, b->stream));
+      HIP_CHECK(launch_step(d_prod, b->L.total, b->dm.shr_total, b->st, 1, 1, true, b->group, false, b->ext, false, false, b->stream));
       HIP_CHECK(hipStreamSynchronize(b->stream));
     }
     batch_launch(b, 1, true);  // mj_forward after load (src/mujoco_system_interface.cpp:741)
@@ -2651,12 +2692,12 @@ void batch_free(BatchImpl* b) {
 int batch_num_envs(const BatchImpl* b) { return b->n; }
 
 int batch_layout(const BatchImpl* b, int* out, int n) {
-  const int v[17] = {b->group, b->dm.L.total, b->dm.S.total, b->dm.blocked, b->dm.pipe_w, b->dm.max_efc,
+  const int v[18] = {b->group, b->dm.L.total, b->dm.S.total, b->dm.blocked, b->dm.pipe_w, b->dm.max_efc,
                      b->dm.max_con, b->dm.ntree, b->dm.shr_total, b->dm.rf_common, b->g16_one_wg,
                      b->group == 16 ? b->wpb16 : 0, b->helpers, b->dm.fuse_ih, b->dm.rf_sweep, b->dm.sens_every,
-                     b->dm.cfrc_contact ? 1 : 0};
+                     b->dm.cfrc_contact ? 1 : 0, b->dm.dyn_mask};
   int k = 0;
-  for (; k < n && k < 17; ++k) out[k] = v[k];
+  for (; k < n && k < 18; ++k) out[k] = v[k];
   return k;
 }
 
@@ -2978,7 +3019,7 @@ void batch_launch(BatchImpl* b, int n_steps, bool forward_only) {
   DevState st = b->st;
   if (b->ctrl_bound) st.ctrl = const_cast<float*>(b->ctrl_bound);  // (read only: loaded at launch start)
   HIP_CHECK(launch_step(b->d_dm, b->L.total, b->dm.shr_total, st, b->n, n_steps, forward_only, b->group,
-                        b->model->solver != MRS_SOL_PGS, b->ext, b->dm.prm_mask != 0, b->stream));
+                        b->model->solver != MRS_SOL_PGS, b->ext, b->dm.prm_mask != 0, b->dm.dyn_mask != 0, b->stream));
   if (timed) HIP_CHECK(hipEventRecord(b->ev1[0], b->stream));
   b->ev_valid[0] = timed;
 }
@@ -3259,6 +3300,65 @@ void batch_get_contact_wrench(BatchImpl* b, double* host, int env0, int n) {
   check_env_range(*b, env0, n);
   ensure_contact_wrench(*b);
   rows_to_host(*b, env0, n, {{env_array(*b, kArrContactWrench), host}});
+}
+
+// the dynamics outputs (mrs.h MRS_DYNOUT_*): the sites the two site outputs cover, an output's floats per
+// env, its device buffer (made on first use, which turns it on for every later launch) and host rows
+void batch_set_jac_sites(BatchImpl* b, const int* site_ids, int n) {
+  const Model& m = *b->model;
+  if (n < 0 || n > MRS_MAX_JAC_SITES) throw std::invalid_argument("site count out of range");
+  if (n > 0 && !site_ids) throw std::invalid_argument("null site list");
+  for (int k = 0; k < n; ++k) {
+    if (site_ids[k] < 0 || site_ids[k] >= m.nsite) throw std::invalid_argument("site id out of range");
+    for (int q = 0; q < k; ++q)
+      if (site_ids[q] == site_ids[k]) throw std::invalid_argument("duplicate site id");
+  }
+  // Nothing has changed up to here: a rejected call leaves the selection and the buffers as they were.
+  // From here on the order keeps a failure harmless: the new buffers are made first (a failed allocation
+  // leaves the batch as it was), then the model block with them is uploaded, and only then are the old
+  // buffers freed -- the device block never names freed memory
+  HIP_CHECK(hipSetDevice(b->device));
+  HIP_CHECK(hipStreamSynchronize(b->stream));
+  DevModel nd = b->dm;
+  nd.dyn_nsel = n;
+  for (int k = 0; k < MRS_MAX_JAC_SITES; ++k) nd.dyn_site[k] = k < n ? site_ids[k] : 0;
+  const int dims[2] = {n * 6 * m.nv, n * 12};
+  const int which[2] = {MRS_DYNOUT_SITE_JAC, MRS_DYNOUT_SITE_POSE};
+  float* old[2] = {b->dm.dyn_out[which[0]], b->dm.dyn_out[which[1]]};
+  auto release = [&](float* p) {
+    if (!p) return;
+    b->allocs.erase(std::remove(b->allocs.begin(), b->allocs.end(), static_cast<void*>(p)), b->allocs.end());
+    (void)hipFree(p);
+  };
+  try {
+    for (int k = 0; k < 2; ++k) {
+      const int w = which[k];
+      nd.dyn_out[w] = nullptr;
+      nd.dyn_mask &= ~(1 << w);
+      if (!(b->dyn_asked & (1 << w)) || dims[k] == 0) continue;
+      nd.dyn_out[w] = static_cast<float*>(dalloc(*b, static_cast<size_t>(b->n) * dims[k] * sizeof(float)));
+      nd.dyn_mask |= 1 << w;
+    }
+    HIP_CHECK(hipStreamSynchronize(b->stream));
+    HIP_CHECK(hipMemcpy(b->d_dm, &nd, sizeof(DevModel), hipMemcpyHostToDevice));
+  } catch (...) {
+    for (int k = 0; k < 2; ++k) release(nd.dyn_out[which[k]]);
+    throw;
+  }
+  b->dm = nd;
+  for (int k = 0; k < 2; ++k) release(old[k]);
+}
+
+int batch_dyn_dim(const BatchImpl* b, int which) { return dyn_dim(*b, which); }
+
+float* batch_dyn_device_ptr(BatchImpl* b, int which) { return ensure_dyn(*b, which); }
+
+void batch_get_dyn(BatchImpl* b, int which, double* host, int env0, int n) {
+  check_env_range(*b, env0, n);
+  // (a site output with no site selected has no elements: nothing is copied, and host may be null)
+  if (!host && n > 0 && dyn_dim(*b, which) > 0) throw std::invalid_argument("null host buffer");
+  ensure_dyn(*b, which);
+  rows_to_host(*b, env0, n, {{env_array(*b, kArrDyn0 + which), host}});
 }
 
 // fp32 field rows [env0, env0 + n) into a caller device buffer [n][dim], ordered on the batch stream

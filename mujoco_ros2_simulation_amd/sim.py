@@ -40,6 +40,10 @@ RESTATE_NEWTON_REFINE, RESTATE_PGS_ELLIPTIC_BLOCK, RESTATE_NO_MPR_POLISH, RESTAT
 INERTIAL_BODY_MASS, INERTIAL_BODY_INERTIA, INERTIAL_DOF_ARMATURE, INERTIAL_COUNT = 0, 1, 2, 3
 # per-env model parameters (MRS_PARAM_*; Batch.get_model_param / set_model_param)
 PARAM_ACT_GAINPRM, PARAM_ACT_BIASPRM, PARAM_DOF_DAMPING, PARAM_GEOM_FRICTION = range(4)
+# the dynamics outputs (MRS_DYNOUT_*; Batch.dyn / dyn_device_ptr / set_jac_sites).  Not DYN_*: those are
+# the actuator dyntypes below
+DYNOUT_QFRC_BIAS, DYNOUT_MASS_MATRIX, DYNOUT_SITE_JAC, DYNOUT_SITE_POSE, DYNOUT_COUNT = 0, 1, 2, 3, 4
+MAX_JAC_SITES = 16
 # ActuatorType (include/mujoco_ros2_control/data.hpp:43-51 numbering)
 ACT_UNKNOWN, ACT_MOTOR, ACT_POSITION, ACT_VELOCITY, ACT_CUSTOM = range(5)
 
@@ -276,6 +280,12 @@ def lib() -> C.CDLL:
             L.mrs_batch_contact_wrench_device_ptr.restype = C.c_void_p
             L.mrs_batch_contact_wrench_device_ptr.argtypes = [C.c_void_p]
             L.mrs_batch_get_contact_wrench.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        if hasattr(L, "mrs_batch_get_dyn"):  # (likewise)
+            L.mrs_batch_set_jac_sites.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            L.mrs_batch_dyn_dim.argtypes = [C.c_void_p, C.c_int]
+            L.mrs_batch_dyn_device_ptr.restype = C.c_void_p
+            L.mrs_batch_dyn_device_ptr.argtypes = [C.c_void_p, C.c_int]
+            L.mrs_batch_get_dyn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.mrs_batch_get_field_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.mrs_batch_last_kernel_ms.restype = C.c_double
         L.mrs_batch_last_kernel_ms.argtypes = [C.c_void_p, C.c_int]
@@ -420,6 +430,8 @@ LAYOUT_KEYS = ["group", "lds_floats", "scratch_floats", "blocked", "pipe_w", "ma
 # the values after them: the batch's optional outputs, 1 once asked for (contact_wrench: the net contact
 # wrench per body, Batch.contact_wrench)
 LAYOUT_OUTPUT_KEYS = ["contact_wrench"]
+# and after those: the dynamics outputs that are on, a bit mask (1 << DYNOUT_*)
+LAYOUT_DYN_KEYS = ["dyn_outputs"]
 
 
 class Batch:
@@ -617,7 +629,7 @@ class Batch:
     def layout(self) -> dict:
         """kernel configuration of this batch (diagnostics): group width, LDS and scratch floats per
         env, blocked mode, pipe width, row and contact capacity, kinematic trees"""
-        keys = LAYOUT_KEYS + LAYOUT_OUTPUT_KEYS
+        keys = LAYOUT_KEYS + LAYOUT_OUTPUT_KEYS + LAYOUT_DYN_KEYS
         out = np.zeros(len(keys), dtype=np.int32)
         k = lib().mrs_debug_batch_layout(self._h, out.ctypes.data, len(keys))
         return dict(zip(keys[:k], out[:k].tolist()))
@@ -722,6 +734,41 @@ class Batch:
         p = lib().mrs_batch_contact_wrench_device_ptr(self._h)
         if not p:
             raise MrsError(lib().mrs_last_status() or -3, lib().mrs_last_error().decode())
+        return p
+
+    def set_jac_sites(self, sites) -> None:
+        """the sites (ids or names, at most MAX_JAC_SITES, no duplicates) that DYNOUT_SITE_JAC and
+        DYNOUT_SITE_POSE cover, in this order; changing the selection remakes their buffers zero-filled"""
+        ids = [self.model.name2id(OBJ_SITE, s) if isinstance(s, str) else int(s) for s in sites]
+        arr = np.asarray(ids, dtype=np.int32)
+        _check(lib().mrs_batch_set_jac_sites(self._h, arr.ctypes.data if len(ids) else None, len(ids)))
+
+    def dyn_dim(self, which: int) -> int:
+        """floats per env of dynamics output `which`"""
+        d = lib().mrs_batch_dyn_dim(self._h, which)
+        if d < 0:
+            _check(d)
+        return d
+
+    def dyn(self, which: int, env0: int = 0, n: int | None = None) -> np.ndarray:
+        """dynamics output `which` (DYNOUT_*) of the last launch: qfrc_bias [n, nv], the dense mass matrix
+        [n, nv, nv], the selected sites' Jacobians [n, nsel, 6, nv] (jacp rows, then jacr, world frame) or
+        poses [n, nsel, 12] (site_xpos, then site_xmat row-major).  They belong to the forward pass that
+        wrote sensordata: after step() the state before the last step's integration, after forward() the
+        current one.  The first call (or dyn_device_ptr) turns the output on: zeros until a step or
+        forward has been launched after it"""
+        nv = self.model.nv
+        dim = self.dyn_dim(which)
+        shape = {DYNOUT_QFRC_BIAS: (nv,), DYNOUT_MASS_MATRIX: (nv, nv),
+                 DYNOUT_SITE_JAC: (dim // max(1, 6 * nv), 6, nv), DYNOUT_SITE_POSE: (dim // 12, 12)}[which]
+        return self._get_rows(lib().mrs_batch_get_dyn, (which,), [shape], env0, n)[0]
+
+    def dyn_device_ptr(self, which: int) -> int | None:
+        """dynamics output `which` on the device, fp32 [n_envs, dim], ordered on the batch stream; turns
+        the output on for all later launches.  None for a site output while no site is selected"""
+        p = lib().mrs_batch_dyn_device_ptr(self._h, which)
+        if not p and lib().mrs_last_status() != MRS_OK:
+            raise MrsError(lib().mrs_last_status(), lib().mrs_last_error().decode())
         return p
 
     def get_device(self, field: int, dptr: int, env0: int = 0, n: int | None = None) -> None:
