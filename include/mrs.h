@@ -412,6 +412,12 @@ int mrs_debug_phase_cycles(double* out, int n, int reset);
  * are selected).
  * Returns the number of values written. */
 int mrs_debug_batch_layout(const mrs_batch* b, int* out, int n);
+/* diagnostics: values [0] to [15] above as mrs_batch_create would choose them for n_envs environments on
+ * a device with cu_count compute units (<= 0: unknown, as when the query fails) and max_contacts (<= 0:
+ * from the model), without a device: the environment switches are read, the model's tables built and
+ * the plan chosen, nothing else.  Returns the number of values written, MRS_ERR_INVALID for a null or
+ * bad argument, MRS_ERR_UNSUPPORTED for a model mrs_batch_create refuses with it. */
+int mrs_debug_plan_layout(const mrs_model* m, int n_envs, int cu_count, int max_contacts, int* out, int n);
 
 #ifdef __cplusplus
 }

@@ -562,4 +562,14 @@ int mrs_debug_batch_layout(const mrs_batch* b, int* out, int n) {
   return mrs::batch_layout(b->impl, out, n);
 }
 
+int mrs_debug_plan_layout(const mrs_model* m, int n_envs, int cu_count, int max_contacts, int* out, int n) {
+  int k = 0;
+  const int rc = guarded([&] {
+    if (!m || !out || n < 0) throw std::invalid_argument("null model or output");
+    if (n_envs < 1) throw std::invalid_argument("n_envs must be positive");
+    k = mrs::plan_layout(m->m, n_envs, cu_count, max_contacts, out, n);
+  });
+  return rc == MRS_OK ? k : rc;
+}
+
 }  // extern "C"

@@ -16,6 +16,8 @@ BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_cont
 void batch_free(BatchImpl* b);
 int batch_num_envs(const BatchImpl* b);
 int batch_layout(const BatchImpl* b, int* out, int n);  // diagnostics: kernel configuration
+// its first 16 values as a batch of n_envs on a device with cu_count CUs would have them (no device)
+int plan_layout(const Model& m, int n_envs, int cu_count, int max_contacts, int* out, int n);
 void batch_set_stream(BatchImpl* b, void* stream);
 void batch_reset(BatchImpl* b, int key, int env0, int n);
 // start-state pool (count rows; qvel may be null: zeros; count 0 frees it) and the masked reset

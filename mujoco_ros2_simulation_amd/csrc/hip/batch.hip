@@ -4,13 +4,10 @@
 
 #include <algorithm>
 #include <cmath>
-#include <array>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <functional>
 #include <initializer_list>
 #include <stdexcept>
 #include <string>
@@ -23,6 +20,8 @@
 #include "../mjcf/model.h"
 #include "batch.h"
 #include "devmodel.h"
+#include "devtables.h"
+#include "plan.h"
 #include "raymesh.h"
 #include "lit.h"
 #include "start_rows.h"
@@ -939,29 +938,6 @@ __global__ __launch_bounds__(256) void reset_masked_kernel(const ResetArgs a) {
   if (lane == 4) a.time[e] = t;
 }
 
-// ------------------------------------------------------------------ packing helpers
-struct Packer {
-  std::vector<float> f;
-  std::vector<int> i;
-  std::vector<std::pair<CPtr<float>*, size_t>> fptr;
-  std::vector<std::pair<CPtr<int>*, size_t>> iptr;
-  void addf(CPtr<float>* dst, const std::vector<double>& v) {
-    fptr.emplace_back(dst, f.size());
-    for (double x : v) f.push_back(static_cast<float>(x));
-    while (f.size() % 4) f.push_back(0);
-  }
-  void addf(CPtr<float>* dst, const std::vector<float>& v) {
-    fptr.emplace_back(dst, f.size());
-    f.insert(f.end(), v.begin(), v.end());
-    while (f.size() % 4) f.push_back(0);
-  }
-  void addi(CPtr<int>* dst, const std::vector<int>& v) {
-    iptr.emplace_back(dst, i.size());
-    i.insert(i.end(), v.begin(), v.end());
-    while (i.size() % 4) i.push_back(0);
-  }
-};
-
 }  // namespace
 
 // ------------------------------------------------------------------ Batch implementation
@@ -1035,1272 +1011,9 @@ void* dalloc(BatchImpl& b, size_t bytes) {
   return p;
 }
 
-// Per-mesh bounding volume hierarchy for rays (rangefinders, depth and colour): a binary tree over a
-// mesh's triangles in depth-first order; each node stores its AABB, inflated by 1e-5 of the mesh's
-// extent so that the fp32 slab test never rejects a triangle that Moller-Trumbore hits, and the index
-// of the node after its subtree (stackless traversal, raymesh.h).  Leaves hold up to 4 consecutive
-// triangles of the mesh's device face list, which is reordered for it (face ids stay relative to the
-// mesh's vertices; only ties between triangles at equal ray parameter can pick a different triangle).
-// Meshes of at most 64 triangles keep no hierarchy: a wave tests their triangles with scalar loads.
-void build_mesh_bvh(const Model& m, std::vector<int>& face_out, std::vector<float>& node,
-                    std::vector<int>& adr, std::vector<int>& num) {
-  face_out = m.mesh_face;
-  const int nmesh = static_cast<int>(m.mesh_faceadr.size());
-  adr.assign(std::max(1, nmesh), 0);
-  num.assign(std::max(1, nmesh), 0);
-  auto fbits = [](int v) { float f; std::memcpy(&f, &v, sizeof f); return f; };
-  for (int k = 0; k < nmesh; ++k) {
-    const int fa = m.mesh_faceadr[k], fn = m.mesh_facenum[k], va = m.mesh_vertadr[k];
-    adr[k] = static_cast<int>(node.size() / 8);
-    if (fn <= 64 || std::getenv("MRS_NO_BVH")) continue;  // MRS_NO_BVH: every triangle (tests' A/B)
-    struct Tri { double lo[3], hi[3], c[3]; int f[3]; };
-    std::vector<Tri> tris(fn);
-    double mlo[3] = {1e300, 1e300, 1e300}, mhi[3] = {-1e300, -1e300, -1e300};
-    for (int f = 0; f < fn; ++f) {
-      Tri& t = tris[f];
-      for (int c = 0; c < 3; ++c) { t.lo[c] = 1e300; t.hi[c] = -1e300; t.f[c] = m.mesh_face[3 * (fa + f) + c]; }
-      for (int v = 0; v < 3; ++v)
-        for (int c = 0; c < 3; ++c) {
-          const double x = m.mesh_vert[3 * (va + t.f[v]) + c];
-          t.lo[c] = std::min(t.lo[c], x); t.hi[c] = std::max(t.hi[c], x);
-        }
-      for (int c = 0; c < 3; ++c) {
-        t.c[c] = 0.5 * (t.lo[c] + t.hi[c]);
-        mlo[c] = std::min(mlo[c], t.lo[c]); mhi[c] = std::max(mhi[c], t.hi[c]);
-      }
-    }
-    const double pad = 1e-5 * std::max(1e-9, std::max(mhi[0] - mlo[0], std::max(mhi[1] - mlo[1], mhi[2] - mlo[2])));
-    const int leaf = std::getenv("MRS_BVH_LEAF") ? std::max(1, std::min(64, std::atoi(std::getenv("MRS_BVH_LEAF")))) : 4;
-    std::vector<float> nodes;
-    std::function<void(int, int)> build = [&](int b, int e) {
-      const int me = static_cast<int>(nodes.size() / 8);
-      double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, clo[3] = {1e300, 1e300, 1e300},
-             chi[3] = {-1e300, -1e300, -1e300};
-      for (int i = b; i < e; ++i)
-        for (int c = 0; c < 3; ++c) {
-          lo[c] = std::min(lo[c], tris[i].lo[c]); hi[c] = std::max(hi[c], tris[i].hi[c]);
-          clo[c] = std::min(clo[c], tris[i].c[c]); chi[c] = std::max(chi[c], tris[i].c[c]);
-        }
-      for (int c = 0; c < 3; ++c) nodes.push_back(static_cast<float>(lo[c] - pad));
-      nodes.push_back(0);
-      for (int c = 0; c < 3; ++c) nodes.push_back(static_cast<float>(hi[c] + pad));
-      nodes.push_back(fbits(-1));
-      if (e - b <= leaf) {
-        nodes[8 * me + 7] = fbits((b << 8) | (e - b));
-      } else {
-        // binned surface-area heuristic (16 centroid bins per axis): the split minimising
-        // N_left A_left + N_right A_right, i.e. the expected triangle tests of a ray that enters the
-        // node; the median of the longest axis when no bin boundary separates the centroids
-        constexpr int kBins = 16;
-        auto area = [](const double* l, const double* h) {
-          const double dx = h[0] - l[0], dy = h[1] - l[1], dz = h[2] - l[2];
-          return dx * dy + dy * dz + dz * dx;
-        };
-        int best_ax = -1, best_s = 0;
-        double best_cost = 1e300;
-        for (int ax = 0; ax < 3; ++ax) {
-          const double ext = chi[ax] - clo[ax];
-          if (ext <= 1e-12) continue;
-          int cnt[kBins] = {};
-          double blo[kBins][3], bhi[kBins][3];
-          for (int q = 0; q < kBins; ++q)
-            for (int c = 0; c < 3; ++c) { blo[q][c] = 1e300; bhi[q][c] = -1e300; }
-          for (int i = b; i < e; ++i) {
-            const int q = std::min(kBins - 1, static_cast<int>((tris[i].c[ax] - clo[ax]) / ext * kBins));
-            ++cnt[q];
-            for (int c = 0; c < 3; ++c) { blo[q][c] = std::min(blo[q][c], tris[i].lo[c]); bhi[q][c] = std::max(bhi[q][c], tris[i].hi[c]); }
-          }
-          double rl[kBins][3], rh[kBins][3];
-          int rn[kBins];
-          for (int c = 0; c < 3; ++c) { rl[kBins - 1][c] = blo[kBins - 1][c]; rh[kBins - 1][c] = bhi[kBins - 1][c]; }
-          rn[kBins - 1] = cnt[kBins - 1];
-          for (int q = kBins - 2; q >= 0; --q) {
-            rn[q] = rn[q + 1] + cnt[q];
-            for (int c = 0; c < 3; ++c) { rl[q][c] = std::min(rl[q + 1][c], blo[q][c]); rh[q][c] = std::max(rh[q + 1][c], bhi[q][c]); }
-          }
-          double ll[3] = {1e300, 1e300, 1e300}, lh[3] = {-1e300, -1e300, -1e300};
-          int ln = 0;
-          for (int q = 1; q < kBins; ++q) {
-            ln += cnt[q - 1];
-            for (int c = 0; c < 3; ++c) { ll[c] = std::min(ll[c], blo[q - 1][c]); lh[c] = std::max(lh[c], bhi[q - 1][c]); }
-            if (ln == 0 || rn[q] == 0) continue;
-            const double cost = ln * area(ll, lh) + rn[q] * area(rl[q], rh[q]);
-            if (cost < best_cost) { best_cost = cost; best_ax = ax; best_s = q; }
-          }
-        }
-        int mid = (b + e) / 2;
-        if (best_ax >= 0 && !std::getenv("MRS_BVH_MEDIAN")) {
-          const double ext = chi[best_ax] - clo[best_ax];
-          const int ax = best_ax, sp = best_s;
-          const double lo0 = clo[ax];
-          auto it = std::partition(tris.begin() + b, tris.begin() + e, [&](const Tri& t) {
-            return std::min(kBins - 1, static_cast<int>((t.c[ax] - lo0) / ext * kBins)) < sp;
-          });
-          mid = static_cast<int>(it - tris.begin());
-        } else {
-          int ax = 0;
-          for (int c = 1; c < 3; ++c)
-            if (chi[c] - clo[c] > chi[ax] - clo[ax]) ax = c;
-          std::nth_element(tris.begin() + b, tris.begin() + mid, tris.begin() + e,
-                           [ax](const Tri& x, const Tri& y) { return x.c[ax] < y.c[ax]; });
-        }
-        build(b, mid);
-        build(mid, e);
-      }
-      nodes[8 * me + 3] = fbits(static_cast<int>(nodes.size() / 8));
-    };
-    build(0, fn);
-    for (int f = 0; f < fn; ++f)
-      for (int c = 0; c < 3; ++c) face_out[3 * (fa + f) + c] = tris[f].f[c];
-    num[k] = static_cast<int>(nodes.size() / 8);
-    node.insert(node.end(), nodes.begin(), nodes.end());
-  }
-  if (node.empty()) node.assign(8, 0.0f);
-}
-
-void build_devmodel(BatchImpl& b, int max_con_req) {
-  const Model& m = *b.model;
-  DevModel& d = b.dm;
-  if (m.nv > 64) throw UnsupportedError("nv > 64 is not supported by the one-wave-per-env kernel");
-  for (int s = 0; s < m.nsensor; ++s) {
-    int t = m.sensor_type[s];
-    if (t == MRS_SENS_ACCELEROMETER) d.acc_sens |= 1;
-    if (t == MRS_SENS_FORCE || t == MRS_SENS_TORQUE) d.acc_sens |= 3;
-    if (t == MRS_SENS_FRAMELINACC) d.acc_sens |= 1;  // reads cacc
-    if (t == MRS_SENS_TOUCH) d.acc_sens |= 2;        // reads the row forces
-  }
-  d.na = m.na;
-  d.nmocap = m.nmocap;
-  // a body whose world pose is the same in every env for good: welded to the world and not on or
-  // below a mocap body (whose pose is per-env state)
-  auto fixed_in_world = [&](int body) {
-    return m.body_weldid[body] == 0 && m.body_mocapid[m.body_rootid[body]] < 0;
-  };
-  d.nq = m.nq; d.nv = m.nv; d.nu = m.nu; d.nbody = m.nbody; d.njnt = m.njnt; d.ngeom = m.ngeom;
-  d.nsite = m.nsite; d.ncam = m.ncam; d.nsensor = m.nsensor; d.nsensordata = m.nsensordata;
-  d.max_depth = m.max_depth;
-  d.integrator = m.integrator; d.iterations = m.iterations; d.disableflags = m.disableflags;
-  d.solver = m.solver; d.ls_iterations = m.ls_iterations; d.cone = m.cone; d.restate = m.restate;
-  if (std::getenv("MRS_NO_MULTICCD")) d.restate |= MRS_RESTATE_NO_MULTICCD;  // (A/B of the face contacts)
-  d.impratio = static_cast<float>(m.impratio); d.ls_tolerance = static_cast<float>(m.ls_tolerance);
-  // diagnostic phase ablation for profiling only (bit 0 sensors, 1 collision, 2 constraints)
-  d.diag_skip = std::getenv("MRS_DIAG_SKIP") ? std::atoi(std::getenv("MRS_DIAG_SKIP")) : 0;
-  // a fused launch evaluates the sensors on its last step only (step.hip step_kernel);
-  // MRS_SENSORS_EVERY_STEP=1 evaluates them every step (A/B: the same outputs, bit for bit)
-  d.sens_every = std::getenv("MRS_SENSORS_EVERY_STEP") && std::atoi(std::getenv("MRS_SENSORS_EVERY_STEP")) != 0 ? 1 : 0;
-  d.timestep = static_cast<float>(m.timestep);
-  d.timestep_d = m.timestep;
-  d.tolerance = static_cast<float>(m.tolerance);
-  d.pgs_scale = solver_scale(m.stat_meaninertia, m.nv);
-  for (int i = 0; i < 3; ++i) d.gravity[i] = static_cast<float>(m.gravity[i]);
-
-  // --- host precomputation of flat lists
-  std::vector<int> subtree_end(m.nbody);
-  for (int bI = m.nbody - 1; bI >= 0; --bI) {
-    int e = bI + 1;
-    while (e < m.nbody) {
-      int x = e;
-      bool inside = false;
-      while (x != 0) { if (x == bI) { inside = true; break; } x = m.body_parentid[x]; }
-      if (bI == 0) inside = true;
-      if (!inside) break;
-      ++e;
-    }
-    subtree_end[bI] = e;
-  }
-  std::vector<int> level_adr(m.max_depth + 2, 0), level_num(m.max_depth + 2, 0), level_body;
-  for (int lev = 1; lev <= m.max_depth; ++lev) {
-    level_adr[lev] = static_cast<int>(level_body.size());
-    for (int bI = 1; bI < m.nbody; ++bI)
-      if (m.body_depth[bI] == lev) level_body.push_back(bI);
-    level_num[lev] = static_cast<int>(level_body.size()) - level_adr[lev];
-  }
-  // pointer-jumping tables for the tree passes: jump[r][b] = ancestor of b at distance 2^r when b
-  // is deeper than 2^r (that ancestor is not the world body), else -1; ceil(log2(max_depth)) rounds
-  d.kin_onepass = 1;
-  for (int bI = 0; bI < m.nbody; ++bI) {
-    const int nj = m.body_jntnum[bI];
-    if (nj > 1) d.kin_onepass = 0;
-    if (nj == 1) {
-      const int t = m.jnt_type[m.body_jntadr[bI]];
-      if (t != MRS_JNT_HINGE && t != MRS_JNT_FREE) d.kin_onepass = 0;
-    }
-  }
-  if (std::getenv("MRS_KIN_TWOPASS")) d.kin_onepass = 0;  // A/B: the joint frames from a second pass
-  d.njump = 0;
-  while ((1 << d.njump) < m.max_depth) ++d.njump;
-  std::vector<int> jump(std::max(1, d.njump * m.nbody), -1);
-  for (int r = 0; r < d.njump; ++r)
-    for (int bI = 1; bI < m.nbody; ++bI) {
-      if (m.body_depth[bI] <= (1 << r)) continue;
-      int a = bI;
-      for (int k = 0; k < (1 << r); ++k) a = m.body_parentid[a];
-      jump[r * m.nbody + bI] = a;
-    }
-  std::vector<int> Mpair;
-  for (int i = 0; i < m.nv; ++i)
-    for (int j = i; j >= 0; j = m.dof_parentid[j]) { Mpair.push_back(i); Mpair.push_back(j); }
-  d.nMpair = static_cast<int>(Mpair.size() / 2);
-  // static collision-pair filter (mj_collision broad phase minus the dynamic bounding test)
-  std::vector<int> pg1, pg2, pdim;
-  std::vector<float> pmargin, pgap, pfric, psolref, psolimp;
-  {
-    // explicit <contact><pair>s first, with their own parameters (mj_collision collides them before
-    // the dynamic pairs; mrs::Model::expair_*)
-    for (size_t q = 0; q < m.expair_geom1.size(); ++q) {
-      const int ga = m.expair_geom1[q], gb = m.expair_geom2[q];
-      const int ta = m.geom_type[ga], tb = m.geom_type[gb];
-      if ((ta == MRS_GEOM_PLANE && tb == MRS_GEOM_PLANE) || ta == MRS_GEOM_HFIELD || tb == MRS_GEOM_HFIELD)
-        throw UnsupportedError("explicit pair of geom types " + std::to_string(ta) + "/" + std::to_string(tb) +
-                               " is not implemented");
-      pg1.push_back(ga); pg2.push_back(gb);
-      pdim.push_back(m.expair_dim[q]);
-      pmargin.push_back(static_cast<float>(m.expair_margin[q]));
-      pgap.push_back(static_cast<float>(m.expair_gap[q]));
-      // (sliding, torsional, rolling) as the mixed pairs store them
-      pfric.push_back(static_cast<float>(m.expair_friction[5 * q]));
-      pfric.push_back(static_cast<float>(m.expair_friction[5 * q + 2]));
-      pfric.push_back(static_cast<float>(m.expair_friction[5 * q + 3]));
-      for (int i = 0; i < 2; ++i) psolref.push_back(static_cast<float>(m.expair_solref[2 * q + i]));
-      for (int i = 0; i < 5; ++i) psolimp.push_back(static_cast<float>(m.expair_solimp[5 * q + i]));
-    }
-    // the compiler's statically admissible pairs (mrs::Model::pair_geom1/2, lower geom type first)
-    for (size_t q = 0; q < m.pair_geom1.size(); ++q) {
-        const int ga = m.pair_geom1[q], gb = m.pair_geom2[q];
-        const int g1 = std::min(ga, gb), g2 = std::max(ga, gb);
-        int ta = m.geom_type[ga], tb = m.geom_type[gb];
-        // every pair of the implemented types: dedicated primitives, plane-ellipsoid/cylinder/mesh,
-        // and MPR for the rest (step.hip narrowphase); plane-plane pairs (a plane on a moving body
-        // against another plane) are skipped, as mj_collision has no plane-plane collider; hfields
-        // are absent
-        if (ta == MRS_GEOM_PLANE && tb == MRS_GEOM_PLANE) continue;
-        bool ok = ta != MRS_GEOM_HFIELD && tb != MRS_GEOM_HFIELD;
-        if (!ok)
-          throw UnsupportedError("collision pair of geom types " + std::to_string(ta) + "/" + std::to_string(tb) +
-                                 " is not implemented (geoms " + std::to_string(g1) + "," + std::to_string(g2) + ")");
-        pg1.push_back(ga); pg2.push_back(gb);
-        pdim.push_back(std::max(m.geom_condim[ga], m.geom_condim[gb]));
-        pmargin.push_back(static_cast<float>(std::max(m.geom_margin[ga], m.geom_margin[gb])));
-        pgap.push_back(static_cast<float>(std::max(m.geom_gap[ga], m.geom_gap[gb])));
-        double s1 = m.geom_solmix[ga], s2 = m.geom_solmix[gb], mix;
-        if (s1 >= 1e-15 && s2 >= 1e-15) mix = s1 / (s1 + s2);
-        else if (s1 < 1e-15 && s2 < 1e-15) mix = 0.5;
-        else mix = s1 < 1e-15 ? 0 : 1;
-        for (int i = 0; i < 3; ++i)
-          pfric.push_back(static_cast<float>(std::max(m.geom_friction[3 * ga + i], m.geom_friction[3 * gb + i])));
-        for (int i = 0; i < 2; ++i)
-          psolref.push_back(static_cast<float>(mix * m.geom_solref[2 * ga + i] + (1 - mix) * m.geom_solref[2 * gb + i]));
-        for (int i = 0; i < 5; ++i)
-          psolimp.push_back(static_cast<float>(mix * m.geom_solimp[5 * ga + i] + (1 - mix) * m.geom_solimp[5 * gb + i]));
-      }
-  }
-  d.npair = static_cast<int>(pg1.size());
-  d.npair_explicit = static_cast<int>(m.expair_geom1.size());
-  b.pair_g1 = pg1;
-  b.pair_dim = pdim;
-  b.pair_mu.resize(pg1.size());
-  for (size_t q = 0; q < pg1.size(); ++q) b.pair_mu[q] = pfric[3 * q];
-  // active equality constraints (rows first in the solver order, as mj_makeConstraint)
-  std::vector<int> eq_t, eq_o1, eq_o2;
-  std::vector<double> eq_sr, eq_si, eq_dat;
-  d.neq = d.neq_rows = 0;
-  if (!(m.disableflags & (MRS_DSBL_EQUALITY | MRS_DSBL_CONSTRAINT)))
-    for (size_t q = 0; q < m.eq_type.size(); ++q) {
-      if (!m.eq_active0[q]) continue;
-      eq_t.push_back(m.eq_type[q]); eq_o1.push_back(m.eq_obj1id[q]); eq_o2.push_back(m.eq_obj2id[q]);
-      eq_sr.insert(eq_sr.end(), &m.eq_solref[2 * q], &m.eq_solref[2 * q] + 2);
-      eq_si.insert(eq_si.end(), &m.eq_solimp[5 * q], &m.eq_solimp[5 * q] + 5);
-      eq_dat.insert(eq_dat.end(), &m.eq_data[MRS_NEQDATA * q], &m.eq_data[MRS_NEQDATA * q] + MRS_NEQDATA);
-      d.neq_rows += m.eq_type[q] == MRS_EQ_CONNECT ? 3 : (m.eq_type[q] == MRS_EQ_WELD ? 6 : 1);
-    }
-  d.neq = static_cast<int>(eq_t.size());
-  // fixed tendons: wraps (qpos / dof address, coefficient), the constant Jacobian rows (dense
-  // ntendon x nv), per tendon 12 constants (stiffness, damping, lengthspring[2], range[2], margin,
-  // frictionloss, invweight0), and the tendons that give friction-loss / limit rows
-  const int ntendon = static_cast<int>(m.tendon_adr.size());
-  std::vector<int> ten_adr(m.tendon_adr), ten_num(m.tendon_num), wrap_qadr, wrap_dof, ten_fric, ten_lim;
-  std::vector<double> wrap_coef(m.wrap_prm), tenJ(static_cast<size_t>(ntendon) * m.nv, 0.0), tenprm;
-  for (size_t k = 0; k < m.wrap_objid.size(); ++k) {
-    wrap_qadr.push_back(m.jnt_qposadr[m.wrap_objid[k]]);
-    wrap_dof.push_back(m.jnt_dofadr[m.wrap_objid[k]]);
-  }
-  for (int t = 0; t < ntendon; ++t) {
-    for (int k = m.tendon_adr[t]; k < m.tendon_adr[t] + m.tendon_num[t]; ++k)
-      tenJ[static_cast<size_t>(t) * m.nv + wrap_dof[k]] += m.wrap_prm[k];
-    const double pr[12] = {m.tendon_stiffness[t], m.tendon_damping[t], m.tendon_lengthspring[2 * t],
-                           m.tendon_lengthspring[2 * t + 1], m.tendon_range[2 * t], m.tendon_range[2 * t + 1],
-                           m.tendon_margin[t], m.tendon_frictionloss[t], m.tendon_invweight0[t], 0, 0, 0};
-    tenprm.insert(tenprm.end(), pr, pr + 12);
-    if (!(m.disableflags & (MRS_DSBL_FRICTIONLOSS | MRS_DSBL_CONSTRAINT)) && m.tendon_frictionloss[t] > 0)
-      ten_fric.push_back(t);
-    if (!(m.disableflags & (MRS_DSBL_LIMIT | MRS_DSBL_CONSTRAINT)) && m.tendon_limited[t]) ten_lim.push_back(t);
-  }
-  d.ntendon = ntendon;
-  d.nten_fric = static_cast<int>(ten_fric.size());
-  d.nten_lim = static_cast<int>(ten_lim.size());
-  // rows outside the blocked-mode sparse solver's kinds (equality, tendon friction / limits): the
-  // dense row path runs instead
-  d.xrows = d.neq + d.nten_fric + d.nten_lim;
-  b.pair_g2 = pg2;
-  // kinematic trees (bodies sharing a root child of the world) that own dofs: their dofs are one
-  // contiguous range, M is block diagonal over them, and constraint rows touch at most two of them
-  // (mj_island's trees).  Blocked mode stores M / its factor per tree and solves the constraint rows
-  // sparsely over the trees they touch (csrc/hip/step.hip constraints_sparse).
-  std::vector<int> body_tree(m.nbody, -1), dof_tree(std::max(1, m.nv), -1), tree_dofadr, tree_dofnum, tree_Moff;
-  {
-    std::vector<int> root_tree(m.nbody, -1);
-    for (int bI = 1; bI < m.nbody; ++bI) {
-      if (m.body_dofnum[bI] == 0) continue;
-      const int r = m.body_rootid[bI];
-      if (root_tree[r] < 0) {
-        root_tree[r] = static_cast<int>(tree_dofadr.size());
-        tree_dofadr.push_back(m.body_dofadr[bI]);
-        tree_dofnum.push_back(0);
-      }
-    }
-    for (int bI = 1; bI < m.nbody; ++bI) body_tree[bI] = root_tree[m.body_rootid[bI]];
-    for (int j = 0; j < m.nv; ++j) {
-      const int t = body_tree[m.dof_bodyid[j]];
-      if (t < 0 || j != tree_dofadr[t] + tree_dofnum[t])
-        throw UnsupportedError("dofs of a kinematic tree are not contiguous");
-      dof_tree[j] = t;
-      ++tree_dofnum[t];
-    }
-    int off = 0;
-    d.tree_nmax = 0;
-    for (size_t t = 0; t < tree_dofadr.size(); ++t) {
-      tree_Moff.push_back(off);
-      off += tree_dofnum[t] * tree_dofnum[t];
-      d.tree_nmax = std::max(d.tree_nmax, tree_dofnum[t]);
-    }
-    d.ntree = static_cast<int>(tree_dofadr.size());
-    d.nMblk = off;
-    // pipe width of the sparse solver: dof slots of the widest row (two trees for a contact)
-    int widest = 1;
-    for (int j = 0; j < m.nv; ++j) widest = std::max(widest, tree_dofnum[dof_tree[j]]);
-    for (size_t p = 0; p < pg1.size(); ++p) {
-      const int t1 = body_tree[m.geom_bodyid[pg1[p]]], t2 = body_tree[m.geom_bodyid[pg2[p]]];
-      int w = (t1 >= 0 ? tree_dofnum[t1] : 0) + (t2 >= 0 && t2 != t1 ? tree_dofnum[t2] : 0);
-      widest = std::max(widest, w);
-    }
-    d.pipe_w = 8;
-    while (d.pipe_w < widest) d.pipe_w *= 2;
-  }
-  d.sparse_off = std::getenv("MRS_SPARSE_OFF") ? std::atoi(std::getenv("MRS_SPARSE_OFF")) & 15 : 0;
-  std::vector<int> fric, lim, rf;
-  for (int j = 0; j < m.nv; ++j) if (m.dof_frictionloss[j] > 0) fric.push_back(j);
-  for (int j = 0; j < m.njnt; ++j)
-    if (m.jnt_limited[j] && (m.jnt_type[j] == MRS_JNT_HINGE || m.jnt_type[j] == MRS_JNT_SLIDE)) lim.push_back(j);
-  // sensors by kernel path: rangefinders (the ray passes), the velocity / axis / subtree / touch types
-  // (step.hip sensors_more, entered only by models that have one), the others (step.hip sensors)
-  auto sens_more = [](int t) {
-    return t == MRS_SENS_TOUCH || t == MRS_SENS_VELOCIMETER || t == MRS_SENS_SUBTREECOM || t == MRS_SENS_SUBTREELINVEL ||
-           (t >= MRS_SENS_FRAMEXAXIS && t <= MRS_SENS_FRAMELINACC);
-  };
-  std::vector<int> other_sens, more_sens;
-  for (int s = 0; s < m.nsensor; ++s) {
-    if (m.sensor_type[s] == MRS_SENS_RANGEFINDER) rf.push_back(s);
-    else if (sens_more(m.sensor_type[s])) more_sens.push_back(s);
-    else other_sens.push_back(s);
-  }
-  d.nsens_other = static_cast<int>(other_sens.size());
-  d.nsens_more = static_cast<int>(more_sens.size());
-  d.nfric = static_cast<int>(fric.size());
-  d.nlim = static_cast<int>(lim.size());
-  d.nrf = static_cast<int>(rf.size());
-  // contact capacity per env: requested, or (<= 0) the pairs' own maxima (8 for box-box and
-  // plane-mesh, 4 for the other pairs) clamped to [32, 128]
-  int pair_max = 0;
-  for (size_t p = 0; p < pg1.size(); ++p) {
-    const int ta = m.geom_type[pg1[p]], tb = m.geom_type[pg2[p]];
-    pair_max += (ta == MRS_GEOM_BOX && tb == MRS_GEOM_BOX) || (ta == MRS_GEOM_PLANE && tb == MRS_GEOM_MESH) ? kMaxPairCon : 4;
-  }
-  const int cap = max_con_req > 0 ? max_con_req : std::min(128, std::max(32, pair_max));
-  d.max_con = d.npair == 0 ? 0 : std::min(pair_max, cap);
-  d.max_efc = d.neq_rows + d.nfric + d.nten_fric + 2 * (d.nlim + d.nten_lim) + 4 * d.max_con;
-  // actuators
-  std::vector<int> act_dof, act_qadr;
-  std::vector<float> act_gear, act_gain, act_bias;
-  std::vector<int> act_ten;
-  for (int a = 0; a < m.nu; ++a) {
-    int j = m.actuator_trnid[2 * a];
-    if (m.actuator_trntype[a] == MRS_TRN_TENDON) {
-      // a tendon transmission: the record's qpos / dof addresses hold -1 - tendon (length and
-      // velocity from the step's tendon slot in LDS), its moment is gear * ten_J
-      act_dof.push_back(-1 - j);
-      act_qadr.push_back(-1 - j);
-      act_ten.push_back(j);
-    } else {
-      if (m.jnt_type[j] != MRS_JNT_HINGE && m.jnt_type[j] != MRS_JNT_SLIDE)
-        throw UnsupportedError("actuators on free/ball joints are not supported");
-      act_dof.push_back(m.jnt_dofadr[j]);
-      act_qadr.push_back(m.jnt_qposadr[j]);
-      act_ten.push_back(-1);
-    }
-    act_gear.push_back(static_cast<float>(m.actuator_gear[6 * a]));
-    for (int i = 0; i < 3; ++i) {
-      act_gain.push_back(static_cast<float>(m.actuator_gainprm[MRS_NGAIN * a + i]));
-      act_bias.push_back(static_cast<float>(m.actuator_biasprm[MRS_NBIAS * a + i]));
-    }
-  }
-
-  Packer P;
-  P.addi(&d.body_parentid, m.body_parentid); P.addi(&d.body_rootid, m.body_rootid);
-  P.addi(&d.body_jntnum, m.body_jntnum); P.addi(&d.body_jntadr, m.body_jntadr);
-  P.addi(&d.body_dofnum, m.body_dofnum); P.addi(&d.body_dofadr, m.body_dofadr);
-  P.addi(&d.body_subtree_end, subtree_end); P.addi(&d.level_adr, level_adr);
-  P.addi(&d.level_num, level_num); P.addi(&d.level_body, level_body); P.addi(&d.jump, jump);
-  P.addf(&d.body_pos, m.body_pos); P.addf(&d.body_quat, m.body_quat); P.addf(&d.body_ipos, m.body_ipos);
-  P.addf(&d.body_iquat, m.body_iquat); P.addf(&d.body_mass, m.body_mass);
-  P.addf(&d.body_subtreemass, m.body_subtreemass); P.addf(&d.body_inertia, m.body_inertia);
-  P.addf(&d.body_gravcomp, m.body_gravcomp); P.addf(&d.body_invweight0, m.body_invweight0);
-  P.addi(&d.jnt_type, m.jnt_type); P.addi(&d.jnt_qposadr, m.jnt_qposadr); P.addi(&d.jnt_dofadr, m.jnt_dofadr);
-  P.addi(&d.jnt_bodyid, m.jnt_bodyid); P.addi(&d.jnt_actfrclimited, m.jnt_actfrclimited);
-  P.addf(&d.jnt_pos, m.jnt_pos); P.addf(&d.jnt_axis, m.jnt_axis); P.addf(&d.jnt_stiffness, m.jnt_stiffness);
-  P.addf(&d.jnt_range, m.jnt_range); P.addf(&d.jnt_margin, m.jnt_margin); P.addf(&d.jnt_solref, m.jnt_solref);
-  P.addf(&d.jnt_solimp, m.jnt_solimp); P.addf(&d.jnt_actfrcrange, m.jnt_actfrcrange);
-  P.addi(&d.dof_bodyid, m.dof_bodyid); P.addi(&d.dof_jntid, m.dof_jntid);
-  P.addf(&d.dof_armature, m.dof_armature); P.addf(&d.dof_damping, m.dof_damping);
-  P.addf(&d.dof_frictionloss, m.dof_frictionloss); P.addf(&d.dof_solref, m.dof_solref);
-  P.addf(&d.dof_solimp, m.dof_solimp); P.addf(&d.dof_invweight0, m.dof_invweight0);
-  P.addf(&d.qpos0, m.qpos0); P.addf(&d.qpos_spring, m.qpos_spring);
-  P.addi(&d.Mpair, Mpair);
-  P.addi(&d.body_tree, body_tree); P.addi(&d.dof_tree, dof_tree); P.addi(&d.tree_dofadr, tree_dofadr);
-  P.addi(&d.tree_dofnum, tree_dofnum); P.addi(&d.tree_Moff, tree_Moff);
-  P.addi(&d.geom_type, m.geom_type); P.addi(&d.geom_bodyid, m.geom_bodyid); P.addi(&d.geom_group, m.geom_group);
-  P.addi(&d.geom_dataid, m.geom_dataid);
-  std::vector<int> bvh_face, bvh_adr, bvh_num;
-  std::vector<float> bvh_node;
-  build_mesh_bvh(m, bvh_face, bvh_node, bvh_adr, bvh_num);
-  P.addi(&d.mesh_vertadr, m.mesh_vertadr); P.addi(&d.mesh_faceadr, m.mesh_faceadr); P.addi(&d.mesh_facenum, m.mesh_facenum);
-  P.addi(&d.mesh_hulladr, m.mesh_hulladr); P.addi(&d.mesh_hullnum, m.mesh_hullnum); P.addi(&d.mesh_face, bvh_face);
-  P.addi(&d.mesh_bvhadr, bvh_adr); P.addi(&d.mesh_bvhnum, bvh_num); P.addf(&d.mesh_bvh, bvh_node);
-  P.addi(&d.mesh_hull, m.mesh_hull); P.addf(&d.mesh_vert, m.mesh_vert);
-  P.addi(&d.mesh_polyadr, m.mesh_polyadr); P.addi(&d.mesh_polynum, m.mesh_polynum);
-  P.addi(&d.mesh_polyvertadr, m.mesh_polyvertadr); P.addi(&d.mesh_polyvertnum, m.mesh_polynum_v);
-  P.addi(&d.mesh_polyvert, m.mesh_polyvert); P.addf(&d.mesh_polynormal, m.mesh_polynormal);
-  {
-    // pre-gathered triangle records in device face order: vertex a, b - a, c - a, formed in fp32 from
-    // the fp32 vertices exactly as ray_tri forms them on the device (bit-identical t)
-    std::vector<float> tri(9 * bvh_face.size() / 3);
-    const int nmesh = static_cast<int>(m.mesh_faceadr.size());
-    for (int k = 0; k < nmesh; ++k)
-      for (int f = m.mesh_faceadr[k]; f < m.mesh_faceadr[k] + m.mesh_facenum[k]; ++f) {
-        float v[3][3];
-        for (int c = 0; c < 3; ++c)
-          for (int i = 0; i < 3; ++i) v[c][i] = static_cast<float>(m.mesh_vert[3 * (m.mesh_vertadr[k] + bvh_face[3 * f + c]) + i]);
-        for (int i = 0; i < 3; ++i) {
-          tri[9 * f + i] = v[0][i];
-          tri[9 * f + 3 + i] = v[1][i] - v[0][i];
-          tri[9 * f + 6 + i] = v[2][i] - v[0][i];
-        }
-      }
-    P.addf(&d.mesh_tri, tri);
-  }
-  {
-    // mesh geoms a camera can see (groups 0-2, alpha > 0), for the binning frame kernel; limits of its
-    // records: 64 geom slots, 2^18 triangles per mesh, pairs within an int
-    std::vector<int> rg, rb;
-    long long np = 0;
-    bool ok = true;
-    for (int g = 0; g < m.ngeom; ++g) {
-      if (m.geom_type[g] != MRS_GEOM_MESH || m.geom_group[g] < 0 || m.geom_group[g] > 2 || m.geom_rgba[4 * g + 3] == 0) continue;
-      const int fn = m.mesh_facenum[m.geom_dataid[g]];
-      ok &= fn < (1 << 18);
-      rg.push_back(g);
-      rb.push_back(static_cast<int>(np));
-      np += fn;
-    }
-    ok &= rg.size() <= 64 && np < (1ll << 30) && m.ngeom <= kDepthGeoms;
-    if (!ok) { rg.clear(); rb.clear(); np = 0; }
-    d.nrast = static_cast<int>(rg.size());
-    d.nrast_pair = static_cast<int>(np);
-    P.addi(&d.rast_geom, rg); P.addi(&d.rast_base, rb);
-  }
-  P.addf(&d.geom_size, m.geom_size); P.addf(&d.geom_pos, m.geom_pos); P.addf(&d.geom_quat, m.geom_quat);
-  P.addf(&d.geom_rbound, m.geom_rbound); P.addf(&d.geom_rgba, m.geom_rgba);
-  {
-    // lit.h's rlit block (layout in its header comment); more than kLitMaxLights lights are refused
-    if (static_cast<int>(m.light_active.size()) > kLitMaxLights)
-      throw std::runtime_error("at most " + std::to_string(kLitMaxLights) + " lights are supported");
-    const int nl = static_cast<int>(m.light_active.size()), nm = static_cast<int>(m.mat_texid.size()),
-              nt = static_cast<int>(m.tex_type.size());
-    std::vector<double> r(kLitHead + kLitLight * nl + kLitMat * nm + kLitTex * nt, 0.0);
-    for (int i = 0; i < 10; ++i) r[i] = m.vis_headlight[i];
-    r[10] = nl;
-    d.lit_sky = -1;
-    for (int t = 0; t < nt && d.lit_sky < 0; ++t)
-      if (m.tex_type[t] == MRS_TEX_SKYBOX) d.lit_sky = t;
-    r[11] = d.lit_sky;
-    for (int l = 0; l < nl; ++l) {
-      double* o = r.data() + kLitHead + kLitLight * l;
-      for (int i = 0; i < 3; ++i) {
-        o[i] = m.light_pos[3 * l + i]; o[3 + i] = m.light_dir[3 * l + i];
-        o[6 + i] = m.light_ambient[3 * l + i]; o[9 + i] = m.light_diffuse[3 * l + i];
-        o[12 + i] = m.light_specular[3 * l + i]; o[15 + i] = m.light_attenuation[3 * l + i];
-      }
-      o[18] = std::cos(m.light_cutoff[l] * M_PI / 180); o[19] = m.light_exponent[l];
-      o[20] = m.light_directional[l]; o[21] = m.light_castshadow[l]; o[22] = m.light_active[l];
-    }
-    d.lit_nlight = nl;
-    d.lit_mat0 = kLitHead + kLitLight * nl;
-    d.lit_tex0 = d.lit_mat0 + kLitMat * nm;
-    for (int k = 0; k < nm; ++k) {
-      double* o = r.data() + d.lit_mat0 + kLitMat * k;
-      o[0] = m.mat_texid[k]; o[1] = m.mat_texuniform[k];
-      o[2] = m.mat_texrepeat[2 * k]; o[3] = m.mat_texrepeat[2 * k + 1];
-      o[4] = m.mat_specular[k]; o[5] = m.mat_shininess[k]; o[6] = m.mat_emission[k];
-    }
-    for (int t = 0; t < nt; ++t) {
-      double* o = r.data() + d.lit_tex0 + kLitTex * t;
-      o[0] = m.tex_type[t]; o[1] = m.tex_builtin[t]; o[2] = m.tex_mark[t];
-      o[3] = m.tex_width[t]; o[4] = m.tex_height[t];
-      for (int i = 0; i < 3; ++i) { o[5 + i] = m.tex_rgb1[3 * t + i]; o[8 + i] = m.tex_rgb2[3 * t + i]; o[11 + i] = m.tex_markrgb[3 * t + i]; }
-    }
-    P.addf(&d.rlit, r);
-    std::vector<int> mid(m.ngeom, -1);
-    for (int g = 0; g < m.ngeom && g < static_cast<int>(m.geom_matid.size()); ++g) mid[g] = m.geom_matid[g];
-    P.addi(&d.geom_matid, mid);
-  }
-  P.addi(&d.pair_g1, pg1); P.addi(&d.pair_g2, pg2); P.addi(&d.pair_dim, pdim);
-  P.addi(&d.ten_adr, ten_adr); P.addi(&d.ten_num, ten_num); P.addi(&d.wrap_qadr, wrap_qadr);
-  P.addi(&d.wrap_dof, wrap_dof); P.addf(&d.wrap_coef, wrap_coef); P.addf(&d.ten_J, tenJ);
-  P.addf(&d.ten_prm, tenprm); P.addi(&d.ten_fric, ten_fric); P.addi(&d.ten_lim, ten_lim);
-  P.addf(&d.ten_solref_lim, m.tendon_solref_lim); P.addf(&d.ten_solimp_lim, m.tendon_solimp_lim);
-  P.addf(&d.ten_solref_fri, m.tendon_solref_fri); P.addf(&d.ten_solimp_fri, m.tendon_solimp_fri);
-  P.addi(&d.act_ten, act_ten);
-  P.addi(&d.eq_type, eq_t); P.addi(&d.eq_obj1id, eq_o1); P.addi(&d.eq_obj2id, eq_o2);
-  P.addf(&d.eq_solref, eq_sr); P.addf(&d.eq_solimp, eq_si); P.addf(&d.eq_data, eq_dat);
-  P.addf(&d.pair_margin, pmargin); P.addf(&d.pair_gap, pgap); P.addf(&d.pair_friction, pfric);
-  P.addf(&d.pair_solref, psolref); P.addf(&d.pair_solimp, psolimp);
-  P.addi(&d.site_bodyid, m.site_bodyid); P.addf(&d.site_pos, m.site_pos); P.addf(&d.site_quat, m.site_quat);
-  P.addi(&d.cam_bodyid, m.cam_bodyid); P.addf(&d.cam_pos, m.cam_pos); P.addf(&d.cam_quat, m.cam_quat);
-  P.addi(&d.act_dof, act_dof); P.addi(&d.act_qadr, act_qadr);
-  P.addi(&d.act_gaintype, m.actuator_gaintype); P.addi(&d.act_biastype, m.actuator_biastype);
-  P.addi(&d.act_ctrllimited, m.actuator_ctrllimited); P.addi(&d.act_forcelimited, m.actuator_forcelimited);
-  P.addf(&d.act_gear, act_gear); P.addf(&d.act_gainprm, act_gain); P.addf(&d.act_biasprm, act_bias);
-  P.addf(&d.act_ctrlrange, m.actuator_ctrlrange); P.addf(&d.act_forcerange, m.actuator_forcerange);
-  P.addi(&d.sensor_type, m.sensor_type); P.addi(&d.sensor_objtype, m.sensor_objtype);
-  P.addi(&d.sensor_objid, m.sensor_objid); P.addi(&d.sensor_adr, m.sensor_adr); P.addi(&d.sensor_dim, m.sensor_dim);
-  P.addf(&d.sensor_cutoff, m.sensor_cutoff);
-  P.addi(&d.fric_dof, fric); P.addi(&d.lim_jnt, lim); P.addi(&d.rf_sensor, rf);
-  P.addi(&d.sens_other, other_sens);
-  // friction-loss rows and limited joints, 4 floats each, staged in workgroup LDS (shr_fric, shr_lim):
-  // a friction row's impedance is that of distance 0 at margin 0, so its R and reference stiffness
-  // B are model constants (computed here in fp32, the order the kernel used); limits: qpos address,
-  // margin, range
-  std::vector<float> fricrec, limrec;
-  {
-    auto fbits = [](int v) { float f; std::memcpy(&f, &v, sizeof f); return f; };
-    auto clampf = [](float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); };
-    for (int j : fric) {
-      const float si1 = static_cast<float>(m.dof_solimp[5 * j + 1]);
-      const float dmax = clampf(si1, 0.0001f, 0.9999f);
-      const float R = fric_row_R(m, j, m.dof_invweight0[j]);  // (start_rows.h: an env's inertial row computes it too)
-      const float sr0 = static_cast<float>(m.dof_solref[2 * j]), sr1 = static_cast<float>(m.dof_solref[2 * j + 1]);
-      float B;
-      if (sr0 > 0) {
-        float tc = sr0;
-        if (!(m.disableflags & MRS_DSBL_REFSAFE) && tc < 2 * d.timestep) tc = 2 * d.timestep;
-        B = 2 / (dmax * tc);
-      } else {
-        B = -sr1 / dmax;
-      }
-      fricrec.insert(fricrec.end(), {fbits(j), R, B, static_cast<float>(m.dof_frictionloss[j])});
-    }
-    for (int j : lim)
-      limrec.insert(limrec.end(), {fbits(m.jnt_qposadr[j]), static_cast<float>(m.jnt_margin[j]),
-                                   static_cast<float>(m.jnt_range[2 * j]), static_cast<float>(m.jnt_range[2 * j + 1])});
-  }
-  P.addf(&d.fricrec, fricrec);
-  P.addf(&d.limrec, limrec);
-  // smooth-force tables (step.hip smooth_forces), staged in workgroup LDS: per actuator (20 floats)
-  // qpos / dof address, gear, ctrl limit flag and range, gain type and prm[3], bias type and prm[3],
-  // force limit flag and range; per dof (16 floats) its single actuator (-1 none, -2 several: the
-  // actuator loop runs), that actuator's gear, the joint's actuator-force limit flag and range,
-  // joint type, stiffness, qpos address, qpos_spring, the dof's damping, body, subtree end,
-  // whether any body of the subtree has gravcomp, the dof's friction-loss row (-1 none) and its
-  // joint's first dof
-  std::vector<float> actrec, dofrec;
-  {
-    auto fbits = [](int v) { float f; std::memcpy(&f, &v, sizeof f); return f; };
-    for (int a = 0; a < m.nu; ++a) {
-      std::vector<float> r = {fbits(act_qadr[a]), fbits(act_dof[a]), act_gear[a], fbits(m.actuator_ctrllimited[a]),
-                              static_cast<float>(m.actuator_ctrlrange[2 * a]), static_cast<float>(m.actuator_ctrlrange[2 * a + 1]),
-                              fbits(m.actuator_gaintype[a]), act_gain[3 * a], act_gain[3 * a + 1], act_gain[3 * a + 2],
-                              fbits(m.actuator_biastype[a]), act_bias[3 * a], act_bias[3 * a + 1], act_bias[3 * a + 2],
-                              fbits(m.actuator_forcelimited[a]), static_cast<float>(m.actuator_forcerange[2 * a]),
-                              static_cast<float>(m.actuator_forcerange[2 * a + 1]), 0.0f, 0.0f, 0.0f};
-      actrec.insert(actrec.end(), r.begin(), r.end());
-    }
-    // each dof's friction-loss row (its index in the friction rows, -1 none): the 16-lane register
-    // solvers index the friction rows by dof (step.hip constraints)
-    std::vector<int> fric_row(m.nv, -1);
-    for (size_t k = 0; k < fric.size(); ++k) fric_row[fric[k]] = static_cast<int>(k);
-    for (int j = 0; j < m.nv; ++j) {
-      int act = -1;
-      float gear = 0;
-      for (int a = 0; a < m.nu; ++a) {
-        if (act_dof[a] == j) { act = act == -1 ? a : -2; gear = act_gear[a]; }
-        if (act_ten[a] >= 0 && tenJ[static_cast<size_t>(act_ten[a]) * m.nv + j] != 0) act = -2;  // the loop
-      }
-      const int jid = m.dof_jntid[j], b = m.dof_bodyid[j];
-      int gc = 0;
-      for (int x = b; x < subtree_end[b]; ++x) gc |= m.body_gravcomp[x] != 0;
-      std::vector<float> r = {fbits(act), gear, fbits(m.jnt_actfrclimited[jid]), static_cast<float>(m.jnt_actfrcrange[2 * jid]),
-                              static_cast<float>(m.jnt_actfrcrange[2 * jid + 1]), fbits(m.jnt_type[jid]),
-                              static_cast<float>(m.jnt_stiffness[jid]), fbits(m.jnt_qposadr[jid]),
-                              static_cast<float>(m.qpos_spring[m.jnt_qposadr[jid]]), static_cast<float>(m.dof_damping[j]),
-                              fbits(b), fbits(subtree_end[b]), fbits(gc), fbits(fric_row[j]),
-                              fbits(m.jnt_dofadr[jid]), 0.0f};
-      dofrec.insert(dofrec.end(), r.begin(), r.end());
-    }
-  }
-  P.addf(&d.actrec, actrec);
-  // activation dynamics of the stateful actuators (step.hip act_input / act_next), read only when
-  // na > 0: per actuator (8 floats) dyntype, address in act (-1 stateless), the time constant
-  // max(tau, 1e-15), filterexact's step factor tau (1 - exp(-h / tau)) from fp64, the activation limit
-  // flag and range, actearly
-  std::vector<float> actdyn;
-  if (m.na > 0) {
-    auto fbits = [](int v) { float f; std::memcpy(&f, &v, sizeof f); return f; };
-    for (int a = 0; a < m.nu; ++a) {
-      const double tau = std::max(m.actuator_dynprm[3 * a], 1e-15);
-      const std::vector<float> r = {fbits(m.actuator_dyntype[a]), fbits(m.actuator_actadr[a]), static_cast<float>(tau),
-                                    static_cast<float>(tau * -std::expm1(-m.timestep / tau)),
-                                    fbits(m.actuator_actlimited[a]), static_cast<float>(m.actuator_actrange[2 * a]),
-                                    static_cast<float>(m.actuator_actrange[2 * a + 1]), fbits(m.actuator_actearly[a])};
-      actdyn.insert(actdyn.end(), r.begin(), r.end());
-    }
-  }
-  P.addf(&d.actdyn, actdyn);
-  P.addf(&d.dofrec, dofrec);
-  // tree tables for the smooth dynamics (step.hip com_pos, make_M, com_vel, rne), staged in workgroup
-  // LDS: per body (8 floats) mass, subtree mass, root, parent, subtree end, dof address, dof count,
-  // pad; per (dof, ancestor-dof) pair of M (4 floats) i, j, body of i, armature when i == j
-  std::vector<float> bodytab, mpairtab;
-  {
-    auto fbits = [](int v) { float f; std::memcpy(&f, &v, sizeof f); return f; };
-    for (int b = 0; b < m.nbody; ++b)
-      bodytab.insert(bodytab.end(), {static_cast<float>(m.body_mass[b]), static_cast<float>(m.body_subtreemass[b]),
-                                     fbits(m.body_rootid[b]), fbits(m.body_parentid[b]), fbits(subtree_end[b]),
-                                     fbits(m.body_dofadr[b]), fbits(m.body_dofnum[b]), 0.0f});
-    for (size_t q = 0; q + 1 < Mpair.size(); q += 2) {
-      const int i = Mpair[q], j = Mpair[q + 1];
-      mpairtab.insert(mpairtab.end(), {fbits(i), fbits(j), fbits(m.dof_bodyid[i]),
-                                       i == j ? static_cast<float>(m.dof_armature[i]) : 0.0f});
-    }
-  }
-  P.addf(&d.bodytab, bodytab);
-  P.addf(&d.mpairtab, mpairtab);
-  // kinematics tables (step.hip body_pose / body_frame_out / kinematics / com_pos), staged in workgroup
-  // LDS with lane groups: per body (25 floats) pos[3], quat[4], ipos[3], iquat[4], inertia[3], first
-  // joint, joint count (int bits), pad; per joint (13) pos[3], axis[3], qpos address, type, qpos0 of
-  // the address, body, dof address, the body's root (int bits), pad; per geom (9) body (int bits),
-  // pos[3], quat[4], pad
-  {
-    auto fbits = [](int v) { float f; std::memcpy(&f, &v, sizeof f); return f; };
-    std::vector<float> kb, kj, kg;
-    for (int b = 0; b < m.nbody; ++b) {
-      for (int i = 0; i < 3; ++i) kb.push_back(static_cast<float>(m.body_pos[3 * b + i]));
-      for (int i = 0; i < 4; ++i) kb.push_back(static_cast<float>(m.body_quat[4 * b + i]));
-      for (int i = 0; i < 3; ++i) kb.push_back(static_cast<float>(m.body_ipos[3 * b + i]));
-      for (int i = 0; i < 4; ++i) kb.push_back(static_cast<float>(m.body_iquat[4 * b + i]));
-      for (int i = 0; i < 3; ++i) kb.push_back(static_cast<float>(m.body_inertia[3 * b + i]));
-      kb.push_back(fbits(m.body_jntadr[b]));
-      kb.push_back(fbits(m.body_jntnum[b]));
-      kb.push_back(fbits(m.body_mocapid[b] + 1));  // (0: not a mocap body, as the pad was)
-      while (kb.size() % 25) kb.push_back(0.0f);
-    }
-    for (int j = 0; j < m.njnt; ++j) {
-      for (int i = 0; i < 3; ++i) kj.push_back(static_cast<float>(m.jnt_pos[3 * j + i]));
-      for (int i = 0; i < 3; ++i) kj.push_back(static_cast<float>(m.jnt_axis[3 * j + i]));
-      kj.push_back(fbits(m.jnt_qposadr[j]));
-      kj.push_back(fbits(m.jnt_type[j]));
-      kj.push_back(static_cast<float>(m.qpos0[m.jnt_qposadr[j]]));
-      kj.push_back(fbits(m.jnt_bodyid[j]));
-      kj.push_back(fbits(m.jnt_dofadr[j]));
-      kj.push_back(fbits(m.body_rootid[m.jnt_bodyid[j]]));
-      while (kj.size() % 13) kj.push_back(0.0f);
-    }
-    for (int g = 0; g < m.ngeom; ++g) {
-      kg.push_back(fbits(m.geom_bodyid[g]));
-      for (int i = 0; i < 3; ++i) kg.push_back(static_cast<float>(m.geom_pos[3 * g + i]));
-      for (int i = 0; i < 4; ++i) kg.push_back(static_cast<float>(m.geom_quat[4 * g + i]));
-      kg.push_back(0.0f);
-    }
-    P.addf(&d.kinbody, kb);
-    P.addf(&d.kinjnt, kj);
-    P.addf(&d.kingeom, kg);
-  }
-  // the non-ray sensors' descriptors, 16 floats each (staged in workgroup LDS at shr_sens): type,
-  // objtype, sensordata address, dim (int bits), cutoff, the object's qpos / dof / actuator / body
-  // index (int bits), the root body (int bits), then the site's or geom's local pos[3] and quat[4]
-  std::vector<float> sensrec;
-  {
-    auto fbits = [](int v) { float f; std::memcpy(&f, &v, sizeof f); return f; };
-    for (int sid : other_sens) {
-      const int t = m.sensor_type[sid], ot = m.sensor_objtype[sid], id = m.sensor_objid[sid];
-      int a = id, root = 0;
-      double lp[3] = {0, 0, 0}, lq[4] = {1, 0, 0, 0};
-      if (t == MRS_SENS_JOINTPOS) a = m.jnt_qposadr[id];
-      else if (t == MRS_SENS_JOINTVEL) a = m.jnt_dofadr[id];
-      else if (t == MRS_SENS_ACCELEROMETER || t == MRS_SENS_FORCE || t == MRS_SENS_TORQUE || t == MRS_SENS_GYRO ||
-               ((t == MRS_SENS_FRAMEPOS || t == MRS_SENS_FRAMEQUAT) && ot == MRS_OBJ_SITE)) {
-        a = m.site_bodyid[id];
-        for (int i = 0; i < 3; ++i) lp[i] = m.site_pos[3 * id + i];
-        for (int i = 0; i < 4; ++i) lq[i] = m.site_quat[4 * id + i];
-      } else if ((t == MRS_SENS_FRAMEPOS || t == MRS_SENS_FRAMEQUAT) && ot != MRS_OBJ_BODY) {  // geom
-        a = m.geom_bodyid[id];
-        for (int i = 0; i < 4; ++i) lq[i] = m.geom_quat[4 * id + i];
-      }
-      if (a >= 0 && (t == MRS_SENS_ACCELEROMETER || t == MRS_SENS_FORCE || t == MRS_SENS_TORQUE)) root = m.body_rootid[a];
-      sensrec.insert(sensrec.end(), {fbits(t), fbits(ot), fbits(m.sensor_adr[sid]), fbits(m.sensor_dim[sid]),
-                                     static_cast<float>(m.sensor_cutoff[sid]), fbits(a), fbits(root),
-                                     static_cast<float>(lp[0]), static_cast<float>(lp[1]), static_cast<float>(lp[2]),
-                                     static_cast<float>(lq[0]), static_cast<float>(lq[1]), static_cast<float>(lq[2]),
-                                     static_cast<float>(lq[3]), fbits(id), 0.0f});
-    }
-    // then the records of sensors_more's types, 32 floats each: the same first 15 (the body and the
-    // local pose of the site / geom / body frame; the body's tree root), 15: one past the last body of
-    // the body's subtree (bodies of a subtree are contiguous), 16: the site's shape type (int bits),
-    // 17-19: its size, 20: the subtree's mass
-    for (int sid : more_sens) {
-      const int t = m.sensor_type[sid], ot = m.sensor_objtype[sid], id = m.sensor_objid[sid];
-      int a = id, st = MRS_GEOM_SPHERE;
-      double lp[3] = {0, 0, 0}, lq[4] = {1, 0, 0, 0}, sz[3] = {0, 0, 0};
-      if (ot == MRS_OBJ_SITE) {
-        a = m.site_bodyid[id];
-        for (int i = 0; i < 3; ++i) lp[i] = m.site_pos[3 * id + i];
-        for (int i = 0; i < 4; ++i) lq[i] = m.site_quat[4 * id + i];
-        for (int i = 0; i < 3; ++i) sz[i] = m.site_size[3 * id + i];
-        st = m.site_type[id];
-      } else if (ot == MRS_OBJ_GEOM) {
-        a = m.geom_bodyid[id];
-        for (int i = 0; i < 3; ++i) lp[i] = m.geom_pos[3 * id + i];
-        for (int i = 0; i < 4; ++i) lq[i] = m.geom_quat[4 * id + i];
-      }
-      sensrec.insert(sensrec.end(), {fbits(t), fbits(ot), fbits(m.sensor_adr[sid]), fbits(m.sensor_dim[sid]),
-                                     static_cast<float>(m.sensor_cutoff[sid]), fbits(a), fbits(m.body_rootid[a]),
-                                     static_cast<float>(lp[0]), static_cast<float>(lp[1]), static_cast<float>(lp[2]),
-                                     static_cast<float>(lq[0]), static_cast<float>(lq[1]), static_cast<float>(lq[2]),
-                                     static_cast<float>(lq[3]), fbits(id), fbits(a == 0 ? m.nbody : subtree_end[a]),
-                                     fbits(st), static_cast<float>(sz[0]), static_cast<float>(sz[1]),
-                                     static_cast<float>(sz[2]), static_cast<float>(m.body_subtreemass[a]),
-                                     0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f});
-    }
-  }
-  P.addf(&d.sensrec, sensrec);
-  std::vector<float> rgeom;
-  auto bits = [](int v) { float f; std::memcpy(&f, &v, sizeof f); return f; };
-  for (int g = 0; g < m.ngeom; ++g) {
-    if (m.geom_rgba[4 * g + 3] == 0) continue;
-    rgeom.insert(rgeom.end(), {bits(g), bits(m.geom_type[g]), bits(m.geom_bodyid[g]),
-                               static_cast<float>(m.geom_rbound[g]), static_cast<float>(m.geom_size[3 * g]),
-                               static_cast<float>(m.geom_size[3 * g + 1]), static_cast<float>(m.geom_size[3 * g + 2]),
-                               bits(m.geom_dataid[g])});
-  }
-  d.nrgeom = static_cast<int>(rgeom.size() / 8);
-  P.addf(&d.rgeom, rgeom);
-  // eigenvector of the smallest eigenvalue of a symmetric 3 x 3 matrix (cyclic Jacobi): the normal of
-  // a fan of directions from their sum d d'
-  auto smallest_eigvec = [](const double cov[3][3], double c[3]) {
-    double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    std::memcpy(A, cov, sizeof A);
-    for (int sweep = 0; sweep < 50; ++sweep)
-      for (int p = 0; p < 2; ++p)
-        for (int q = p + 1; q < 3; ++q) {
-          if (std::abs(A[p][q]) < 1e-15) continue;
-          const double th = 0.5 * std::atan2(2 * A[p][q], A[q][q] - A[p][p]);
-          const double cs = std::cos(th), sn = std::sin(th);
-          for (int k = 0; k < 3; ++k) {
-            const double akp = A[k][p], akq = A[k][q];
-            A[k][p] = cs * akp - sn * akq; A[k][q] = sn * akp + cs * akq;
-          }
-          for (int k = 0; k < 3; ++k) {
-            const double apk = A[p][k], aqk = A[q][k];
-            A[p][k] = cs * apk - sn * aqk; A[q][k] = sn * apk + cs * aqk;
-          }
-          for (int k = 0; k < 3; ++k) {
-            const double vkp = V[k][p], vkq = V[k][q];
-            V[k][p] = cs * vkp - sn * vkq; V[k][q] = sn * vkp + cs * vkq;
-          }
-        }
-    int imin = 0;
-    for (int i = 1; i < 3; ++i) if (A[i][i] < A[imin][imin]) imin = i;
-    for (int i = 0; i < 3; ++i) c[i] = V[i][imin];
-  };
-  // ray blocks (kRayBlock consecutive rangefinders) for the level-1 cull.  When every ray of a block
-  // starts at the same point of the same body the block is bounded by a fan fixed in that body's
-  // frame: unit axis a, in-plane direction b and normal c (the least-spread direction of the rays),
-  // in-plane half-angle theta around a and out-of-plane slope eps = max |d.c| (a planar lidar fan
-  // has eps ~ 0).  Blocks without a common origin, or wider than +-80 degrees, test every geom.
-  std::vector<float> rfblk, rfblk_eps;
-  d.nrfblk = 0;
-  if (d.nrgeom <= 32 && d.nrf > 0) {
-    d.nrfblk = (d.nrf + kRayBlock - 1) / kRayBlock;
-    for (int blk = 0; blk < d.nrfblk; ++blk) {
-      const int k0 = blk * kRayBlock, k1 = std::min(d.nrf, k0 + kRayBlock);
-      const int site0 = m.sensor_objid[rf[k0]], body = m.site_bodyid[site0];
-      bool ok = true;
-      std::vector<std::array<double, 3>> dirs;
-      double axis[3] = {0, 0, 0}, cov[3][3] = {};
-      for (int k = k0; k < k1; ++k) {
-        const int site = m.sensor_objid[rf[k]];
-        if (m.site_bodyid[site] != body) ok = false;
-        for (int i = 0; i < 3; ++i)
-          if (std::abs(m.site_pos[3 * site + i] - m.site_pos[3 * site0 + i]) > 1e-9) ok = false;
-        const double* q = &m.site_quat[4 * site];  // z column of the site rotation (ray direction)
-        std::array<double, 3> dz = {2 * (q[1] * q[3] + q[0] * q[2]), 2 * (q[2] * q[3] - q[0] * q[1]),
-                                    q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3]};
-        const double n = std::sqrt(dz[0] * dz[0] + dz[1] * dz[1] + dz[2] * dz[2]);
-        for (int i = 0; i < 3; ++i) { dz[i] /= n; axis[i] += dz[i]; }
-        for (int i = 0; i < 3; ++i)
-          for (int j = 0; j < 3; ++j) cov[i][j] += dz[i] * dz[j];
-        dirs.push_back(dz);
-      }
-      double an = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
-      double c[3] = {0, 0, 1}, bv[3] = {0, 1, 0}, theta = 0, eps = 0;
-      if (an < 1e-6) ok = false;
-      if (ok) {
-        for (int i = 0; i < 3; ++i) axis[i] /= an;
-        // normal of the fan: eigenvector of the smallest eigenvalue of sum d d' (cyclic Jacobi)
-        smallest_eigvec(cov, c);
-        const double ca = c[0] * axis[0] + c[1] * axis[1] + c[2] * axis[2];
-        for (int i = 0; i < 3; ++i) c[i] -= ca * axis[i];
-        const double cn = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-        if (cn < 1e-6) ok = false;
-        else {
-          for (int i = 0; i < 3; ++i) c[i] /= cn;
-          bv[0] = c[1] * axis[2] - c[2] * axis[1];
-          bv[1] = c[2] * axis[0] - c[0] * axis[2];
-          bv[2] = c[0] * axis[1] - c[1] * axis[0];
-          for (auto& dz : dirs) {
-            const double da = dz[0] * axis[0] + dz[1] * axis[1] + dz[2] * axis[2];
-            const double db = dz[0] * bv[0] + dz[1] * bv[1] + dz[2] * bv[2];
-            const double dc = dz[0] * c[0] + dz[1] * c[1] + dz[2] * c[2];
-            theta = std::max(theta, std::abs(std::atan2(db, da)));
-            eps = std::max(eps, std::abs(dc));
-          }
-          if (theta > 1.4) ok = false;
-        }
-      }
-      rfblk.insert(rfblk.end(), {bits(body), bits(ok ? 1 : 0), static_cast<float>(m.site_pos[3 * site0]),
-                                 static_cast<float>(m.site_pos[3 * site0 + 1]), static_cast<float>(m.site_pos[3 * site0 + 2]),
-                                 static_cast<float>(axis[0]), static_cast<float>(axis[1]), static_cast<float>(axis[2]),
-                                 static_cast<float>(bv[0]), static_cast<float>(bv[1]), static_cast<float>(bv[2]),
-                                 static_cast<float>(c[0]), static_cast<float>(c[1]), static_cast<float>(c[2]),
-                                 static_cast<float>(std::cos(theta + 1e-4)), static_cast<float>(std::sin(theta + 1e-4))});
-      rfblk_eps.push_back(static_cast<float>(eps + 1e-6));
-    }
-  }
-  // record: body, flag, origin[3], a[3], b[3], c[3], cos(theta), sin(theta); then eps per block
-  rfblk.insert(rfblk.end(), rfblk_eps.begin(), rfblk_eps.end());
-  // every ray of the lidar(s) from one point of one body: the pass loop reuses one frame
-  d.rf_common = d.nrfblk > 0 ? 1 : 0;
-  for (int blk = 0; blk < d.nrfblk && d.rf_common; ++blk) {
-    const float* r0 = &rfblk[0];
-    const float* ri = &rfblk[16 * blk];
-    int f; std::memcpy(&f, &ri[1], 4);
-    if (!f || std::memcmp(&ri[0], &r0[0], 4) != 0 || ri[2] != r0[2] || ri[3] != r0[3] || ri[4] != r0[4]) d.rf_common = 0;
-  }
-  // static lidars: when every rangefinder sits on a world-welded body, that body's world pose never
-  // changes, so the ray blocks' fan frames and the rays' origins / directions go to the world frame
-  // here (fp64) and the step kernel skips the per-step body rotation (rf_static_frame)
-  d.rf_static_frame = 0;
-  if (d.nrf > 0) {
-    bool all_static = true;
-    for (int k = 0; k < d.nrf; ++k) all_static = all_static && fixed_in_world(m.site_bodyid[m.sensor_objid[rf[k]]]);
-    d.rf_static_frame = all_static && !std::getenv("MRS_NO_STATIC_FRAME") ? 1 : 0;
-  }
-  auto body_world = [&](int b, double R[9], double p[3]) {  // world pose of a body without joints above it
-    double q[4] = {1, 0, 0, 0};
-    p[0] = p[1] = p[2] = 0;
-    std::vector<int> chain;
-    for (int x = b; x != 0; x = m.body_parentid[x]) chain.push_back(x);
-    for (auto it = chain.rbegin(); it != chain.rend(); ++it) {
-      const double* bp = &m.body_pos[3 * *it];
-      const double* bq = &m.body_quat[4 * *it];
-      const double Rq[9] = {q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3], 2 * (q[1] * q[2] - q[0] * q[3]),
-                            2 * (q[1] * q[3] + q[0] * q[2]), 2 * (q[1] * q[2] + q[0] * q[3]),
-                            q[0] * q[0] - q[1] * q[1] + q[2] * q[2] - q[3] * q[3], 2 * (q[2] * q[3] - q[0] * q[1]),
-                            2 * (q[1] * q[3] - q[0] * q[2]), 2 * (q[2] * q[3] + q[0] * q[1]),
-                            q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3]};
-      for (int i = 0; i < 3; ++i) p[i] += Rq[3 * i] * bp[0] + Rq[3 * i + 1] * bp[1] + Rq[3 * i + 2] * bp[2];
-      const double t[4] = {q[0] * bq[0] - q[1] * bq[1] - q[2] * bq[2] - q[3] * bq[3],
-                           q[0] * bq[1] + q[1] * bq[0] + q[2] * bq[3] - q[3] * bq[2],
-                           q[0] * bq[2] - q[1] * bq[3] + q[2] * bq[0] + q[3] * bq[1],
-                           q[0] * bq[3] + q[1] * bq[2] - q[2] * bq[1] + q[3] * bq[0]};
-      const double tn = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2] + t[3] * t[3]);
-      for (int i = 0; i < 4; ++i) q[i] = t[i] / tn;
-    }
-    R[0] = q[0] * q[0] + q[1] * q[1] - q[2] * q[2] - q[3] * q[3]; R[1] = 2 * (q[1] * q[2] - q[0] * q[3]);
-    R[2] = 2 * (q[1] * q[3] + q[0] * q[2]); R[3] = 2 * (q[1] * q[2] + q[0] * q[3]);
-    R[4] = q[0] * q[0] - q[1] * q[1] + q[2] * q[2] - q[3] * q[3]; R[5] = 2 * (q[2] * q[3] - q[0] * q[1]);
-    R[6] = 2 * (q[1] * q[3] - q[0] * q[2]); R[7] = 2 * (q[2] * q[3] + q[0] * q[1]);
-    R[8] = q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3];
-  };
-  if (d.rf_static_frame) {
-    for (int blk = 0; blk < d.nrfblk; ++blk) {
-      float* r = &rfblk[16 * blk];
-      int body;
-      std::memcpy(&body, &r[0], 4);
-      double R[9], p[3];
-      body_world(body, R, p);
-      for (int v = 0; v < 4; ++v) {  // origin (a point), then a, b, c (directions)
-        const double x[3] = {r[2 + 3 * v], r[3 + 3 * v], r[4 + 3 * v]};
-        for (int i = 0; i < 3; ++i)
-          r[2 + 3 * v + i] = static_cast<float>(R[3 * i] * x[0] + R[3 * i + 1] * x[1] + R[3 * i + 2] * x[2] + (v == 0 ? p[i] : 0.0));
-      }
-    }
-  }
-  P.addf(&d.rfblk, rfblk);
-  // per-ray records: unit direction (z column of the site rotation) and sensordata address first
-  // (one 16-byte load when the ray's pass shares body and origin), then body and origin in the body
-  // frame (the world frame for static lidars)
-  std::vector<float> rfray;
-  for (int k = 0; k < d.nrf; ++k) {
-    const int site = m.sensor_objid[rf[k]];
-    const double* q = &m.site_quat[4 * site];
-    double dz[3] = {2 * (q[1] * q[3] + q[0] * q[2]), 2 * (q[2] * q[3] - q[0] * q[1]),
-                    q[0] * q[0] - q[1] * q[1] - q[2] * q[2] + q[3] * q[3]};
-    const double n = std::sqrt(dz[0] * dz[0] + dz[1] * dz[1] + dz[2] * dz[2]);
-    double dir[3] = {dz[0] / n, dz[1] / n, dz[2] / n}, org[3] = {m.site_pos[3 * site], m.site_pos[3 * site + 1], m.site_pos[3 * site + 2]};
-    if (d.rf_static_frame) {
-      double R[9], p[3];
-      body_world(m.site_bodyid[site], R, p);
-      const double d0[3] = {dir[0], dir[1], dir[2]}, o0[3] = {org[0], org[1], org[2]};
-      for (int i = 0; i < 3; ++i) {
-        dir[i] = R[3 * i] * d0[0] + R[3 * i + 1] * d0[1] + R[3 * i + 2] * d0[2];
-        org[i] = p[i] + R[3 * i] * o0[0] + R[3 * i + 1] * o0[1] + R[3 * i + 2] * o0[2];
-      }
-    }
-    rfray.insert(rfray.end(), {static_cast<float>(dir[0]), static_cast<float>(dir[1]), static_cast<float>(dir[2]),
-                               bits(m.sensor_adr[rf[k]]), bits(m.site_bodyid[site]),
-                               static_cast<float>(org[0]), static_cast<float>(org[1]), static_cast<float>(org[2])});
-  }
-  P.addf(&d.rfray, rfray);
-
-  b.dblock_f = dalloc(b, P.f.size() * sizeof(float));
-  b.dblock_i = dalloc(b, P.i.size() * sizeof(int));
-  HIP_CHECK(hipMemcpyAsync(b.dblock_f, P.f.data(), P.f.size() * sizeof(float), hipMemcpyHostToDevice, b.stream));
-  HIP_CHECK(hipMemcpyAsync(b.dblock_i, P.i.data(), P.i.size() * sizeof(int), hipMemcpyHostToDevice, b.stream));
-  for (auto& kv : P.fptr) kv.first->p = static_cast<const float*>(b.dblock_f) + kv.second;
-  for (auto& kv : P.iptr) kv.first->p = static_cast<const int*>(b.dblock_i) + kv.second;
-  HIP_CHECK(hipStreamSynchronize(b.stream));
-
-  // --- LDS layout (floats).  Dense mode: M and its factor as nv x nv.  Blocked mode (one env per
-  // wave, G = 64): M and its factor per kinematic tree, row forces and the island scratch of the
-  // sparse constraint solver.
-  LdsLayout& L = b.dm.L;
-  int off = 0;
-  auto take = [&](int n) { int o = off; off += n; off = (off + 3) & ~3; return o; };
-  const int nb = m.nbody, nj = std::max(1, m.njnt), nv = std::max(1, m.nv), ng = std::max(1, m.ngeom);
-  bool want_lh = false;  // the helper waves' integrator factor (set once the helpers are decided)
-  auto lds_layout = [&](bool blocked) {
-    off = 0;
-    L.xpos = take(3 * nb); L.xquat = take(4 * nb); L.xmat = take(9 * nb); L.xipos = take(3 * nb);
-    L.xanchor = take(3 * nj); L.xaxis = take(3 * nj); L.gxpos = take(3 * ng); L.gxmat = take(9 * ng);
-    L.scom = take(3 * nb); L.cinert = take(10 * nb); L.crb = d.acc_sens ? take(10 * nb) : 0; L.cdof = take(6 * nv);
-    L.cdofdot = take(6 * nv); L.cvel = take(6 * nb); L.cacc = take(6 * nb); L.cfrc = take(6 * nb);
-    // without accelerometer / force / torque sensors (no rne_post), crb shares cacc + cfrc (12 nb):
-    // CRBA's composite inertias are dead before mj_rne starts, and mj_rne's subtree force sums
-    // (6 per body at crb) overwrite only cacc, which is dead once cfrc is built
-    if (!d.acc_sens) L.crb = L.cacc;
-    const int msize = blocked ? std::max(1, d.nMblk) : nv * nv;
-    L.M = take(msize); L.L = take(msize); L.qpos = take(std::max(1, m.nq)); L.qvel = take(nv);
-    L.ctrl = take(std::max(1, m.nu)); L.qfrc_applied = take(nv); L.qacc_ws = take(nv); L.qfrc_bias = take(nv);
-    L.qfrc_passive = take(nv); L.qfrc_act = take(nv); L.qfrc_smooth = take(nv); L.qacc_smooth = take(nv);
-    L.qacc = take(nv + 1); L.qfrc_con = take(nv + 1);  // + a dummy word (blocked-mode solver)
-    L.act_force = take(std::max(1, m.nu));
-    L.ten = d.ntendon > 0 ? take(2 * d.ntendon) : 0;  // tendon lengths and velocities of the step
-    L.niter = take(1);
-    L.hcon = take(1);
-    L.Lh = want_lh ? take(nv * nv) : 0;
-    L.rfmask = take(std::max(1, d.nrfblk));
-    L.trees = blocked ? take(4 * std::max(1, d.ntree)) : 0;
-    L.dofb = blocked ? take(2 * nv) : 0;
-    // primal solvers in blocked mode: H = M + J'DJ couples the trees a contact joins, so it is
-    // stored dense (dense mode builds H in the factor slot L.L instead)
-    L.H = blocked && m.solver != MRS_SOL_PGS ? take(nv * nv) : 0;
-    L.Li = blocked && m.solver == MRS_SOL_PGS ? take(std::max(1, d.nMblk)) : 0;
-    L.rk = m.integrator == MRS_INT_RK4 ? take(std::max(1, m.nq) + 4 * nv) : 0;
-    L.act = m.na > 0 ? take(4 * m.na) : 0;
-    L.mocap = m.nmocap > 0 ? take(7 * m.nmocap) : 0;
-    L.total = off;
-  };
-  lds_layout(false);
-  // static ray split: every rangefinder on a world-welded body and some ray geom on one too
-  d.rf_mode = 0;
-  d.rf_static_mask = 0;
-  if (d.nrfblk > 0 && d.nrgeom <= 32) {
-    bool static_rays = true;
-    for (int k = 0; k < d.nrf; ++k)
-      if (!fixed_in_world(m.site_bodyid[m.sensor_objid[rf[k]]])) static_rays = false;
-    for (int i = 0, g = 0; g < m.ngeom; ++g) {
-      if (m.geom_rgba[4 * g + 3] == 0) continue;
-      if (fixed_in_world(m.geom_bodyid[g])) d.rf_static_mask |= 1u << i;
-      ++i;
-    }
-    if (static_rays && d.rf_static_mask && !std::getenv("MRS_NO_STATIC_RAYS")) d.rf_mode = 2;
-  }
-  d.rf_static = d.rf_mode ? static_cast<float*>(dalloc(b, std::max(1, d.nrf) * sizeof(float))) : nullptr;
-  // workgroup-shared tables: ray-geom records, the per-ray direction + address when every ray
-  // starts at one point of one body, and the rays' static hits (DevModel::shr_*)
-  int shr_small = 0;
-  auto layout_shared = [&]() {
-    d.shr_rf = d.nrgeom * 8;
-    d.shr_rfst = d.shr_rf + (d.rf_common ? 4 * d.nrf : 0);
-    d.shr_blk = d.shr_rfst + (d.rf_mode == 2 ? d.nrf : 0);
-    d.shr_sens = d.shr_blk + 17 * d.nrfblk;
-    d.shr_fric = d.shr_sens + 16 * d.nsens_other + 32 * d.nsens_more;
-    d.shr_lim = d.shr_fric + 4 * d.nfric;
-    d.shr_act = d.shr_lim + 4 * d.nlim;
-    d.shr_dof = d.shr_act + 20 * m.nu;
-    d.shr_body = d.shr_dof + 16 * m.nv;
-    d.shr_mpair = d.shr_body + 8 * m.nbody;
-    d.shr_jump = d.shr_mpair + 4 * d.nMpair;
-    d.shr_kbody = d.shr_jump + d.njump * m.nbody;
-    d.shr_kjnt = d.shr_kbody + 25 * m.nbody;
-    d.shr_kgeom = d.shr_kjnt + 13 * m.njnt;
-    // the smooth-dynamics tables (from shr_act on) are staged only by lane-group kernels (G < 64);
-    // blocked mode (one env per workgroup) reads them from the model block instead of paying their
-    // LDS per env
-    shr_small = d.shr_act;
-    d.shr_total = d.shr_kgeom + 9 * m.ngeom;
-    d.shr_flag = d.shr_total;  // (helper waves' signal words, one per physics wave)
-    d.shr_total += 4;
-  };
-  layout_shared();
-  // lanes per environment: the narrowest group that still gives every dof its own lane (the
-  // dense M / Cholesky / PGS phases are lane-per-dof) and keeps a workgroup's LDS within 80 KB
-  // (two workgroups per CU); MRS_GROUP overrides (16, 32 or 64)
-  auto lds_bytes = [&](int g) {
-    return (static_cast<size_t>(L.total) * envs_per_block(g) + (g == 64 ? shr_small : d.shr_total)) * sizeof(float);
-  };
-  // (narrow groups win even when they leave CUs idle: C4's 2048 envs run a 10-step launch in
-  // 1.33 ms at G = 16 on 128 workgroups vs 4.0 ms at G = 64 on 512)
-  b.group = 64;
-  for (int g : {32, 16})
-    if (m.nv <= g && lds_bytes(g) <= 80 * 1024) b.group = g;
-  // a 16-lane model whose workgroup tables outgrow the two-per-CU budget (a dense lidar: the per-ray
-  // direction table is 16 B per ray) keeps its 16-lane groups rather than dropping to 32 (~4x slower
-  // on C3): the per-ray table moves out of LDS (rays read from the model block, L1/L2-resident: the
-  // pass's non-common path).  MRS_G16_ONE_WG also allows one workgroup per CU (up to 160 KB)
-  b.g16_one_wg = 0;
-  if (b.group > 16 && m.nv <= 16) {
-    if (d.rf_common) {
-      // drop the common-frame ray table only if that is what lets the 16-lane layout fit; otherwise
-      // the model keeps its wider groups and the table (no silent slowdown of the ray pass)
-      d.rf_common = 0;
-      layout_shared();
-      if (lds_bytes(16) <= 80 * 1024) {
-        b.group = 16;
-      } else {
-        d.rf_common = 1;
-        layout_shared();
-      }
-    }
-    // (one 160 KB workgroup per CU was measured slower than 32-lane groups on the mesh robot: 27 vs
-    // 15 ms per 10-step launch -- a single wave per SIMD cannot hide its memory latency)
-    if (b.group > 16 && lds_bytes(16) <= 160 * 1024 && std::getenv("MRS_G16_ONE_WG")) { b.group = 16; b.g16_one_wg = 1; }
-  }
-  if (const char* e = std::getenv("MRS_GROUP")) {
-    const int g = std::atoi(e);
-    if ((g == 8 || g == 16 || g == 32 || g == 64) && m.nv <= g) b.group = g;
-  }
-  // G = 16 with fewer waves than the device has SIMDs (C4: 2048 envs = 512 waves on 1024 SIMDs):
-  // one-wave workgroups, so the waves spread over every CU instead of filling half of them four to
-  // a CU (measured C4: 0.802 vs 0.822 ms per launch; C3 and C2 have a wave per SIMD or more and keep
-  // four-wave workgroups -- C3's LDS tables per workgroup would cost it residency).  MRS_G16_WPB
-  // overrides (1, 2 or 4)
-  b.wpb16 = WavesPerBlock<16>::value;
-  if (b.group == 16 && !b.g16_one_wg) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b.device) != hipSuccess) cus = 0;
-    const long waves = (static_cast<long>(b.n) * 16 + 63) / 64;
-    if (cus > 0 && waves < 4L * cus) b.wpb16 = 1;
-    if (const char* e = std::getenv("MRS_G16_WPB")) {
-      const int w = std::atoi(e);
-      if (w == 1 || w == 2 || w == 4) b.wpb16 = std::min(w, static_cast<int>(WavesPerBlock<16>::value));
-    }
-  }
-  // extended step kernels (step.hip MRS_EXT) for models with general convex (MPR) pairs -- a pair
-  // that is not plane-* and has an ellipsoid, cylinder or mesh (narrowphase's analytic routines cover
-  // the rest) -- or rangefinders over more than 32 ray geoms
-  b.ext = d.nrgeom > 32 && d.nrf > 0;
-  for (size_t p = 0; p < b.pair_g1.size() && !b.ext; ++p) {
-    const int t1 = m.geom_type[b.pair_g1[p]], t2 = m.geom_type[b.pair_g2[p]];
-    auto conv = [](int t) { return t == MRS_GEOM_ELLIPSOID || t == MRS_GEOM_CYLINDER || t == MRS_GEOM_MESH; };
-    if (t1 != MRS_GEOM_PLANE && t2 != MRS_GEOM_PLANE && (conv(t1) || conv(t2))) b.ext = true;
-  }
-  // helper waves: with one-wave workgroups (fewer waves than SIMDs, so the helpers take SIMDs that
-  // would idle) every physics wave gets a second wave that runs its envs' collision pass, builds their
-  // constraint rows, traces their rangefinders and factors the integrator's M + h D each step while it
-  // runs the dynamics (step_kernel); models with rangefinders (<= 32 ray geoms) without RK4 and
-  // without the extended kernels only.  MRS_RAY_HELPERS=0 turns them off
-  {
-    const char* e = std::getenv("MRS_RAY_HELPERS");
-    const bool want = e ? std::atoi(e) != 0 : true;
-    // (the helper kernels run at one wave per SIMD, step.hip MRS_HELPER_OCC: physics plus helper
-    // waves must fit the device's SIMDs at once, i.e. at most two physics waves per CU)
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b.device) != hipSuccess) cus = 0;
-    const long waves = (static_cast<long>(b.n) * 16 + 63) / 64;
-    const bool fit = cus <= 0 || waves <= 2L * cus;
-    b.helpers = want && fit && b.group == 16 && b.wpb16 == 1 && !b.ext && d.nrf > 0 && d.nrgeom <= 32 &&
-                m.integrator != MRS_INT_RK4 && !(m.disableflags & MRS_DSBL_SENSOR) ? 1 : 0;
-    // the integrator factor slot (implicit-damping Euler and implicitfast; the full implicit
-    // integrator factors its own LU)
-    if (b.helpers && m.integrator != MRS_INT_IMPLICIT) {
-      want_lh = true;
-      lds_layout(false);
-    }
-  }
-  // the integrator's M + h D factored together with M (step.hip cholesky_ih): into M's own LDS slot
-  // for PGS models, which no longer read M after the factor, into the L.Lh slot for Newton / CG
-  // (their primal solve multiplies by M).  16-lane groups without helper waves (they factor it on the
-  // helper), implicitfast, and no force-limited actuator (their velocity derivative depends on the
-  // step's actuator forces, which come after the factor).  MRS_NO_FUSE_IH=1 factors it in integrate()
-  // instead (A/B)
-  {
-    bool flim = false;
-    for (int a = 0; a < m.nu; ++a) flim |= m.actuator_forcelimited[a] != 0;
-    d.fuse_ih = b.group == 16 && !b.helpers && m.integrator == MRS_INT_IMPLICITFAST && !flim && m.nv <= 16 &&
-                !std::getenv("MRS_NO_FUSE_IH") ? 1 : 0;
-    if (d.fuse_ih && m.solver != MRS_SOL_PGS && !want_lh) {
-      want_lh = true;
-      lds_layout(false);
-      if ((static_cast<size_t>(L.total) * envs_per_block(b.group, b.wpb16) + d.shr_total) * sizeof(float) > 160 * 1024) {
-        d.fuse_ih = 0;  // (the extra nv x nv slot does not fit the workgroup's LDS: factor in integrate())
-        want_lh = false;
-        lds_layout(false);
-      }
-    }
-  }
-  // ray sweep (step.hip rays_sweep): a static lidar over a static world (rf_mode 2) whose rays are one
-  // planar, evenly spaced fan from one point -- what <replicate> builds -- and whose sensordata slots
-  // are consecutive.  Each step then computes, per moving ray geom, the interval of ray indices its
-  // bounding sphere can reach, copies the static hit of every ray in no interval and traces only the
-  // rows of G rays that meet one.  The fan is fitted in fp64 over all rays, as the block fit above
-  // does per block; ray k must lie within a quarter increment of phi0 + k dphi.  The helper-wave
-  // kernels keep the block passes.  MRS_NO_RAY_SWEEP=1 forces the block passes (A/B)
-  d.rf_sweep = 0;
-  if (d.rf_mode == 2 && d.rf_common && d.rf_static_frame && d.nrgeom <= 32 && (b.group == 16 || b.group == 32) &&
-      !b.helpers && d.nrf >= 3 && (d.nrf + b.group - 1) / b.group <= 32 && !std::getenv("MRS_NO_RAY_SWEEP")) {
-    bool ok = true;
-    for (int i = 0; i < d.nrgeom; ++i) {
-      int type;
-      std::memcpy(&type, &rgeom[8 * i + 1], 4);
-      if (!((d.rf_static_mask >> i) & 1u) && type == MRS_GEOM_MESH) ok = false;
-    }
-    const int adr0 = m.sensor_adr[rf[0]];
-    for (int k = 0; k < d.nrf; ++k) ok = ok && m.sensor_adr[rf[k]] == adr0 + k;
-    // (the directions the kernel traces: rfray, world frame)
-    auto dir = [&](int k, double v[3]) { for (int i = 0; i < 3; ++i) v[i] = rfray[8 * k + i]; };
-    double cov[3][3] = {}, c[3] = {0, 0, 1}, a[3], bv[3], d0[3];
-    for (int k = 0; k < d.nrf; ++k) {
-      double v[3];
-      dir(k, v);
-      for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) cov[i][j] += v[i] * v[j];
-    }
-    smallest_eigvec(cov, c);
-    dir(0, d0);
-    const double cd = c[0] * d0[0] + c[1] * d0[1] + c[2] * d0[2];
-    for (int i = 0; i < 3; ++i) a[i] = d0[i] - cd * c[i];
-    const double an = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    const double cn = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-    if (an < 0.5 || cn < 0.5) ok = false;
-    double dphi = 0, eps = 0;
-    if (ok) {
-      for (int i = 0; i < 3; ++i) { a[i] /= an; c[i] /= cn; }
-      auto cross_ca = [&]() {
-        bv[0] = c[1] * a[2] - c[2] * a[1];
-        bv[1] = c[2] * a[0] - c[0] * a[2];
-        bv[2] = c[0] * a[1] - c[1] * a[0];
-      };
-      cross_ca();
-      double d1[3];
-      dir(1, d1);
-      if (d1[0] * bv[0] + d1[1] * bv[1] + d1[2] * bv[2] < 0) {  // the sweep runs counter-clockwise about c
-        for (int i = 0; i < 3; ++i) c[i] = -c[i];
-        cross_ca();
-      }
-      // unwrapped in-plane angles (phi0 = 0: a is ray 0), each increment in (0, pi)
-      std::vector<double> phi(d.nrf, 0.0);
-      for (int k = 0; k < d.nrf; ++k) {
-        double v[3];
-        dir(k, v);
-        const double da = v[0] * a[0] + v[1] * a[1] + v[2] * a[2], db = v[0] * bv[0] + v[1] * bv[1] + v[2] * bv[2];
-        eps = std::max(eps, std::abs(v[0] * c[0] + v[1] * c[1] + v[2] * c[2]));
-        if (k == 0) continue;
-        const double kPi = 3.14159265358979323846;
-        double inc = std::atan2(db, da) - std::fmod(phi[k - 1], 2 * kPi);
-        while (inc <= 0) inc += 2 * kPi;
-        if (inc >= kPi) ok = false;
-        phi[k] = phi[k - 1] + inc;
-      }
-      const double kTwoPi = 6.28318530717958647692;
-      dphi = phi[d.nrf - 1] / (d.nrf - 1);
-      // (increments fine enough for fp32 angles to stay well inside the one-ray margin of the intervals)
-      if (!(dphi >= 5e-3) || dphi > 0.5 || eps > 1e-3) ok = false;
-      for (int k = 0; k < d.nrf && ok; ++k) ok = std::abs(phi[k] - k * dphi) <= 0.25 * dphi;
-      // no ray direction twice: the fan ends before ray 0 comes round again
-      if (ok && (d.nrf - 1) * dphi > kTwoPi - 0.5 * dphi) ok = false;
-      if (ok) {
-        d.rf_sw_full = std::abs(d.nrf * dphi - kTwoPi) <= 0.25 * dphi ? 1 : 0;
-        d.rf_sw_plo = static_cast<int>(std::floor(kTwoPi / dphi));
-        d.rf_sw_phi = static_cast<int>(std::ceil(kTwoPi / dphi));
-        d.rf_sw_n = d.nrf;
-        d.rf_sw_adr0 = adr0;
-        for (int i = 0; i < 3; ++i) {
-          d.rf_sw[i] = rfblk[2 + i];  // the origin every pass traces from (and level 1 tests against)
-          d.rf_sw[3 + i] = static_cast<float>(a[i]);
-          d.rf_sw[6 + i] = static_cast<float>(bv[i]);
-          d.rf_sw[9 + i] = static_cast<float>(c[i]);
-        }
-        d.rf_sw[12] = 0.0f;
-        d.rf_sw[13] = static_cast<float>(1.0 / dphi);
-        d.rf_sw[14] = static_cast<float>(eps + 1e-6);
-        d.rf_sw[15] = static_cast<float>(kTwoPi / dphi);
-        d.rf_sweep = 1;
-      }
-    }
-  }
-  d.blocked = b.group == 64 ? 1 : 0;
-  if (b.group == 64) d.shr_total = shr_small;
-
-  if (d.blocked) lds_layout(true);
-  d.shr_off = L.total * envs_per_block(b.group, b.wpb16);
-  if ((static_cast<size_t>(d.shr_off) + d.shr_total) * sizeof(float) > 160 * 1024)
-    throw UnsupportedError("model too large for the per-environment LDS working set");
-  // --- scratch layout (floats).  Dense mode: rows J and M^-1 J' as nefc x nv plus per-row scalars;
-  // blocked mode: one record per row in solver order (J, M^-1 J' and dof per pipe slot, scalars)
-  ScratchLayout& S = b.dm.S;
-  off = 0;
-  const int ne = std::max(1, d.max_efc);
-  // dense rows: dense mode, and blocked mode with a primal solver (the sparse records are PGS's)
-  const int dn = d.blocked && m.solver == MRS_SOL_PGS && m.cone != MRS_CONE_ELLIPTIC && d.xrows == 0 ? 0 : ne;
-  S.efc_J = take(dn * nv); S.efc_MJ = take(dn * nv); S.efc_type = take(ne); S.efc_pos = take(ne);
-  S.efc_margin = take(ne); S.efc_floss = take(ne); S.efc_R = take(dn); S.efc_aref = take(dn);
-  S.efc_b = take(dn); S.efc_f = take(ne); S.efc_ARii = take(dn); S.con = take(kConRec * std::max(1, d.max_con));
-  S.efc_rec = take(d.blocked ? ne * (2 * d.pipe_w + 12) : 0);  // step.hip RF
-  S.efc_rowof = take(d.blocked ? ne : 0);
-  S.efc_item = take(d.blocked ? ne : 0);
-  S.efc_fq = take(d.blocked ? ne : 0);
-  S.efc_hdr = take(d.blocked ? 24 * ne : 0);  // step.hip kHdr
-  S.efc_quad = take(d.blocked ? 64 : 0);
-  S.efc_fd = take(m.cone == MRS_CONE_ELLIPTIC && m.solver == MRS_SOL_PGS ? 2 * ne : 0);  // (16-byte aligned)
-  S.stage = take(d.npair > 0 ? 64 * kMaxPairCon * 7 : 0);  // <= 64 lanes x 8 contacts x 7 floats
-  S.efc_n = take(1);
-  S.sens = take(std::max(1, m.nsensordata));
-  S.xfrc = take(1);
-  S.total = off;
-  b.d_dm = static_cast<DevModel*>(dalloc(b, sizeof(DevModel)));
-  HIP_CHECK(hipMemcpyAsync(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice, b.stream));
-  HIP_CHECK(hipStreamSynchronize(b.stream));
-}
+static_assert(kRlitHead == kLitHead && kRlitLight == kLitLight && kRlitMat == kLitMat && kRlitTex == kLitTex &&
+                  kRlitMaxLights == kLitMaxLights && kRastMaxGeoms == kDepthGeoms,
+              "devtables.h restates lit.h's block layout and the frame kernels' geom limit");
 
 // ---- the per-env arrays: every array [n_envs][dim] that the host reads or writes by env range.  One
 // row of env_array() describes one array -- where the kernels read its pointer (a member of DevState or
@@ -2401,6 +1114,34 @@ void make_env_arrays(BatchImpl& b) {
     if (a.made == EnvArray::ON_USE || (a.made == EnvArray::IF_DIM && a.dim == 0)) continue;
     a.bind(dalloc(b, static_cast<size_t>(b.n) * std::max(1, a.dim) * a.width()));
   }
+}
+
+// The device part of batch creation: the model's tables (devtables.h) and the launch plan (plan.h) are
+// host values; this uploads the two blocks, points DevModel's tables into them, allocates the static
+// ray hits and uploads DevModel.  The arrays make_env_arrays bound to DevModel members stay bound: the
+// env-array table says which they are
+void build_devmodel(BatchImpl& b, int max_con_req, const Overrides& o) {
+  const Model& m = *b.model;
+  const DevTables T = build_tables(m, max_con_req, o);
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b.device) != hipSuccess) cus = 0;
+  const Plan p = choose_plan(m, T, b.n, cus, o);
+  void* made[kArrCount];
+  for (int id = 0; id < kArrCount; ++id) made[id] = env_array(b, id).ptr;
+  b.dm = p.dm;
+  for (int id = 0; id < kArrCount; ++id)
+    if (made[id]) env_array(b, id).bind(made[id]);
+  b.dblock_f = dalloc(b, T.f.size() * sizeof(float));
+  b.dblock_i = dalloc(b, T.i.size() * sizeof(int));
+  HIP_CHECK(hipMemcpyAsync(b.dblock_f, T.f.data(), T.f.size() * sizeof(float), hipMemcpyHostToDevice, b.stream));
+  HIP_CHECK(hipMemcpyAsync(b.dblock_i, T.i.data(), T.i.size() * sizeof(int), hipMemcpyHostToDevice, b.stream));
+  T.patch(b.dm, static_cast<const float*>(b.dblock_f), static_cast<const int*>(b.dblock_i));
+  b.dm.rf_static = b.dm.rf_mode ? static_cast<float*>(dalloc(b, std::max(1, b.dm.nrf) * sizeof(float))) : nullptr;
+  b.group = p.group; b.g16_one_wg = p.g16_one_wg; b.wpb16 = p.wpb16; b.helpers = p.helpers; b.ext = p.ext;
+  b.pair_g1 = T.pair_g1; b.pair_g2 = T.pair_g2; b.pair_dim = T.pair_dim; b.pair_mu = T.pair_mu;
+  b.d_dm = static_cast<DevModel*>(dalloc(b, sizeof(DevModel)));
+  HIP_CHECK(hipMemcpyAsync(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice, b.stream));
+  HIP_CHECK(hipStreamSynchronize(b.stream));  // (the host blocks of T are read until here)
 }
 
 // ---- the two row copies every host accessor goes through.  Each part is an array and the host's fp64
@@ -2618,7 +1359,8 @@ BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_cont
     for (int k = 0; k < 2; ++k) { HIP_CHECK(hipEventCreate(&b->ev0[k])); HIP_CHECK(hipEventCreate(&b->ev1[k])); }
     b->start = start_rows(*model);
     make_env_arrays(*b);
-    build_devmodel(*b, max_contacts);
+    const Overrides o = read_overrides();  // (every batch reads them anew)
+    build_devmodel(*b, max_contacts, o);
     const Model& m = *model;
     const size_t n = static_cast<size_t>(n_envs);
     // padded to whole workgroups of the chosen group width: idle groups use it
@@ -2628,8 +1370,7 @@ BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_cont
     // the first, so a small batch occupies more waves.  Measured slower (round 5, same box: C4 18.2
     // vs 22.9 M env-steps/s at shift 2, C2 147 vs 156 M at shift 1): the mirrors' issue slots cost
     // more than the latency they hide, so it is off by default
-    int shift = 0;
-    if (const char* e = std::getenv("MRS_SPREAD")) shift = std::max(0, std::min(3, std::atoi(e)));
+    const int shift = o.spread;
     const size_t n_virt = ((static_cast<size_t>(n) << shift) + epb - 1) / epb * epb;
     b->st.spread_shift = shift;
     b->st.wpb16 = b->wpb16;
@@ -2692,12 +1433,24 @@ void batch_free(BatchImpl* b) {
 int batch_num_envs(const BatchImpl* b) { return b->n; }
 
 int batch_layout(const BatchImpl* b, int* out, int n) {
-  const int v[18] = {b->group, b->dm.L.total, b->dm.S.total, b->dm.blocked, b->dm.pipe_w, b->dm.max_efc,
-                     b->dm.max_con, b->dm.ntree, b->dm.shr_total, b->dm.rf_common, b->g16_one_wg,
-                     b->group == 16 ? b->wpb16 : 0, b->helpers, b->dm.fuse_ih, b->dm.rf_sweep, b->dm.sens_every,
-                     b->dm.cfrc_contact ? 1 : 0, b->dm.dyn_mask};
+  int v[18];
+  plan_layout_values(b->dm, b->group, b->g16_one_wg, b->wpb16, b->helpers, v);  // (the first 16: plan.h)
+  v[16] = b->dm.cfrc_contact ? 1 : 0;
+  v[17] = b->dm.dyn_mask;
   int k = 0;
   for (; k < n && k < 18; ++k) out[k] = v[k];
+  return k;
+}
+
+// mrs_debug_plan_layout: the overrides, the tables and the plan of a model; touches no device
+int plan_layout(const Model& m, int n_envs, int cu_count, int max_contacts, int* out, int n) {
+  const Overrides o = read_overrides();
+  const DevTables T = build_tables(m, max_contacts, o);
+  const Plan p = choose_plan(m, T, n_envs, cu_count, o);
+  int v[kPlanLayoutValues];
+  plan_layout_values(p.dm, p.group, p.g16_one_wg, p.wpb16, p.helpers, v);
+  int k = 0;
+  for (; k < n && k < kPlanLayoutValues; ++k) out[k] = v[k];
   return k;
 }
 

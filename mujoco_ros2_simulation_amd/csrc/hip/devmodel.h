@@ -19,6 +19,10 @@ namespace mrs {
 // (4): wave-uniform indices become scalar loads (s_load through the scalar cache), per-lane indices
 // become global loads with an SGPR base.  Plain generic pointers loaded from a struct would compile to
 // flat loads with 64-bit per-lane addresses.  Host code sees an ordinary pointer.
+#if !defined(__HIPCC__)  // a plain host compiler (devtables.h, plan.h and their tests): no HIP qualifiers
+#define __device__
+#define __forceinline__ inline
+#endif
 template <class T>
 struct CPtr {
   const T* p;
@@ -32,6 +36,10 @@ struct CPtr {
   }
   __device__ __forceinline__ CPtr operator+(int i) const { return CPtr{p + i}; }
 };
+#if !defined(__HIPCC__)
+#undef __device__
+#undef __forceinline__
+#endif
 
 // LDS layout of one environment (offsets in floats).  One wavefront owns one environment; the
 // workgroup holds 4*64/G environments back to back.
@@ -106,7 +114,7 @@ struct DevModel {
   // at shr_rfst) and tests only the moving geoms; 0: no split.  rf_static_mask: static ray-geom bits.
   int rf_mode, shr_rfst;
   // every rangefinder body is world-welded: rfblk frames and rfray origins / directions are stored
-  // in the world frame (batch.hip), and the kernel uses them without the per-step body rotation
+  // in the world frame (devtables.h), and the kernel uses them without the per-step body rotation
   int rf_static_frame;
   // the ray blocks' level-1 records (rfblk, 16 floats each, then the nrfblk slopes) at shr_blk, the
   // non-ray sensors' descriptors (sensrec, 16 floats each, then sensors_more's 32 each) at shr_sens
@@ -161,7 +169,7 @@ struct DevModel {
   CPtr<int> mesh_polyadr, mesh_polynum, mesh_polyvertadr, mesh_polyvertnum, mesh_polyvert;
   CPtr<float> mesh_polynormal;
   CPtr<float> mesh_vert;
-  // ray hierarchies (batch.hip build_mesh_bvh; mesh_face is reordered to their leaves): per mesh the
+  // ray hierarchies (devtables.h build_mesh_bvh; mesh_face is reordered to their leaves): per mesh the
   // first node and the node count (0: none), 8 floats per node
   CPtr<int> mesh_bvhadr, mesh_bvhnum;
   CPtr<float> mesh_bvh;
@@ -176,7 +184,7 @@ struct DevModel {
   // active equality constraints (mrs_model_view eq_*, inactive ones dropped on the host): neq of
   // them giving neq_rows rows (connect 3, weld 6, joint 1), first in the row order
   int neq, neq_rows;
-  // fixed tendons (batch.hip): wraps, dense Jacobian rows ten_J [ntendon][nv], 12 constants per tendon
+  // fixed tendons (devtables.h tendon_tables): wraps, dense Jacobian rows ten_J [ntendon][nv], 12 constants per tendon
   // (stiffness, damping, lengthspring[2], range[2], margin, frictionloss, invweight0), the tendons
   // with friction-loss rows / limits, each actuator's tendon (-1: joint transmission); xrows: row
   // sources the blocked-mode sparse solver does not take (neq + nten_fric + nten_lim)
@@ -200,14 +208,14 @@ struct DevModel {
   CPtr<int> sensor_type, sensor_objtype, sensor_objid, sensor_adr, sensor_dim;
   CPtr<float> sensor_cutoff;
   CPtr<int> fric_dof, lim_jnt, rf_sensor, sens_other;  // sens_other: non-rangefinder sensor ids
-  CPtr<float> sensrec;  // their descriptors (batch.hip), 16 floats each
+  CPtr<float> sensrec;  // their descriptors (devtables.h sensor_records), 16 floats each
   // velocimeter, frame velocity / acceleration / axis, subtree and touch sensors (step.hip sensors_more):
   // their count; their descriptors, 32 floats each, follow the others' in sensrec and at shr_sens
   int nsens_more;
-  CPtr<float> fricrec, limrec;  // 4 floats per friction-loss dof / limited joint (batch.hip)
-  CPtr<float> actrec, dofrec;   // smooth-force tables (batch.hip)
-  CPtr<float> bodytab, mpairtab;  // tree tables of the smooth dynamics (batch.hip)
-  CPtr<float> kinbody, kinjnt, kingeom;  // kinematics tables (batch.hip; step.hip kin_body / kin_jnt / kin_geom)
+  CPtr<float> fricrec, limrec;  // 4 floats per friction-loss dof / limited joint (devtables.h row_records)
+  CPtr<float> actrec, dofrec;   // smooth-force tables (devtables.h smooth_force_records)
+  CPtr<float> bodytab, mpairtab;  // tree tables of the smooth dynamics (devtables.h tree_records)
+  CPtr<float> kinbody, kinjnt, kingeom;  // kinematics tables (devtables.h kinematics_records; step.hip kin_body / kin_jnt / kin_geom)
   // ray-visible geoms (rgba alpha != 0, what mj_ray tests), packed 8 floats per geom so one wide
   // scalar load fetches a record: geom id, type, body (int bits), rbound, size[3], pad
   CPtr<float> rgeom;
@@ -234,7 +242,7 @@ struct DevModel {
   const float* xfrc;
   // stateful actuators (mjData.act): their count -- 0 for every model without
   // actuator dynamics, whose launches then take none of the activation code -- and the per-actuator
-  // dynamics records (batch.hip actdyn, 8 floats each; packed only when na > 0)
+  // dynamics records (devtables.h smooth_force_records, 8 floats each; packed only when na > 0)
   int na;
   // per-env model parameters in use (below): bit MRS_PARAM_* set once that parameter's buffer exists.
   // Every read site tests this word, not the pointers: it sits beside na and xfrc, which the same

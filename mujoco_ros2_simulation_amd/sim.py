@@ -291,6 +291,7 @@ def lib() -> C.CDLL:
         L.mrs_batch_last_kernel_ms.argtypes = [C.c_void_p, C.c_int]
         L.mrs_debug_phase_cycles.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.mrs_debug_batch_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.mrs_debug_plan_layout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -432,6 +433,16 @@ LAYOUT_KEYS = ["group", "lds_floats", "scratch_floats", "blocked", "pipe_w", "ma
 LAYOUT_OUTPUT_KEYS = ["contact_wrench"]
 # and after those: the dynamics outputs that are on, a bit mask (1 << DYNOUT_*)
 LAYOUT_DYN_KEYS = ["dyn_outputs"]
+
+
+def plan_layout(model: "Model", n_envs: int, cu_count: int, max_contacts: int = 0) -> dict:
+    """the LAYOUT_KEYS part of Batch.layout() as a batch of n_envs on a device with cu_count compute
+    units (0: unknown) would have it, chosen on the host: needs no GPU"""
+    out = np.zeros(len(LAYOUT_KEYS), dtype=np.int32)
+    k = lib().mrs_debug_plan_layout(model.handle, n_envs, cu_count, max_contacts, out.ctypes.data, len(out))
+    if k < 0:
+        raise MrsError(k, lib().mrs_last_error().decode())
+    return dict(zip(LAYOUT_KEYS[:k], out[:k].tolist()))
 
 
 class Batch:
