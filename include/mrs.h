@@ -409,7 +409,10 @@ int mrs_debug_phase_cycles(double* out, int n, int reset);
  * sensors evaluated on every step of a fused launch (MRS_SENSORS_EVERY_STEP=1) instead of the last
  * only, [16] the contact-wrench output on (1; mrs_batch_contact_wrench_device_ptr) or not (0), [17]
  * the dynamics outputs that are on, a bit mask (1 << MRS_DYNOUT_*; a site output's bit only while sites
- * are selected).
+ * are selected), [18] the fused 16-lane solves (1: one reciprocal per lane and solve, qacc_smooth solved
+ * with the friction-loss rows; 0: not a 16-lane PGS batch without helper waves, or MRS_NO_SOLVE_FUSE=1 --
+ * that switch gives the same bits by the separate solves, run out of line: a reference for results, not
+ * for speed).
  * Returns the number of values written. */
 int mrs_debug_batch_layout(const mrs_batch* b, int* out, int n);
 /* diagnostics: values [0] to [15] above as mrs_batch_create would choose them for n_envs environments on

@@ -1433,12 +1433,13 @@ void batch_free(BatchImpl* b) {
 int batch_num_envs(const BatchImpl* b) { return b->n; }
 
 int batch_layout(const BatchImpl* b, int* out, int n) {
-  int v[18];
+  int v[19];
   plan_layout_values(b->dm, b->group, b->g16_one_wg, b->wpb16, b->helpers, v);  // (the first 16: plan.h)
   v[16] = b->dm.cfrc_contact ? 1 : 0;
   v[17] = b->dm.dyn_mask;
+  v[18] = b->dm.solve_fuse;
   int k = 0;
-  for (; k < n && k < 18; ++k) out[k] = v[k];
+  for (; k < n && k < 19; ++k) out[k] = v[k];
   return k;
 }
 

@@ -292,6 +292,11 @@ struct DevModel {
   int dyn_mask, dyn_nsel;
   float* dyn_out[4];
   int dyn_site[16];
+  // 16-lane PGS batches without helper waves: the smooth-force and integrator solves take 1 / L_ii once
+  // per solve from the diagonal's own lane, and the friction-loss fast path solves qacc_smooth as a
+  // ninth column of its substitution (step.hip chol_solve_rows16, pgs_small16_qacc); 0
+  // (MRS_NO_SOLVE_FUSE=1, A/B): separate solves.  Kept last: the fields above keep their offsets
+  int solve_fuse;
 };
 constexpr int kRayBlock = 128;
 // bits of DevModel::prm_mask (1 << MRS_PARAM_*)

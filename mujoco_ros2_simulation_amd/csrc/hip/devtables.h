@@ -34,6 +34,10 @@ struct Overrides {
   bool g16_one_wg = false;   // MRS_G16_ONE_WG: allow 16 lanes with one workgroup per CU (up to 160 KB of LDS)
   bool ray_helpers = true;   // MRS_RAY_HELPERS=0: no helper waves
   bool no_fuse_ih = false;   // MRS_NO_FUSE_IH: factor M + h D in integrate(), not beside M
+  // MRS_NO_SOLVE_FUSE: the 16-lane solves separate, a divide per level (DevModel::solve_fuse).  A
+  // bit-identity reference only, not a speed baseline: the separate form then runs out of line, slower
+  // than it ran before the fused form existed
+  bool no_solve_fuse = false;
   bool no_ray_sweep = false; // MRS_NO_RAY_SWEEP: a static planar lidar keeps the block passes
   bool no_static_rays = false;   // MRS_NO_STATIC_RAYS: no static ray split (rf_mode 0)
   bool no_static_frame = false;  // MRS_NO_STATIC_FRAME: ray tables stay in the body frame
@@ -57,6 +61,7 @@ inline Overrides read_overrides() {
   o.g16_one_wg = set("MRS_G16_ONE_WG");
   o.ray_helpers = num("MRS_RAY_HELPERS", 1) != 0;
   o.no_fuse_ih = set("MRS_NO_FUSE_IH");
+  o.no_solve_fuse = set("MRS_NO_SOLVE_FUSE");
   o.no_ray_sweep = set("MRS_NO_RAY_SWEEP");
   o.no_static_rays = set("MRS_NO_STATIC_RAYS");
   o.no_static_frame = set("MRS_NO_STATIC_FRAME");

@@ -289,6 +289,11 @@ inline Plan choose_plan(const Model& m, const DevTables& T, int n_envs, int cu_c
     if (with_lh * sizeof(float) > 160 * 1024) d.fuse_ih = 0;
     else p.want_lh = true;
   }
+  // the 16-lane register solves with one reciprocal per lane and qacc_smooth solved with the
+  // friction-loss rows (step.hip chol_solve_rows16, pgs_small16_qacc): PGS batches without helper
+  // waves.  MRS_NO_SOLVE_FUSE=1: the separate solves with a divide per level, out of line (a reference
+  // for the bits, not for speed)
+  d.solve_fuse = p.group == 16 && m.solver == MRS_SOL_PGS && !p.helpers && !o.no_solve_fuse ? 1 : 0;
   // the helper-wave kernels keep the block passes.  MRS_NO_RAY_SWEEP=1 forces them (A/B)
   if (d.rf_mode == 2 && d.rf_common && d.rf_static_frame && d.nrgeom <= 32 && (p.group == 16 || p.group == 32) &&
       !p.helpers && d.nrf >= 3 && (d.nrf + p.group - 1) / p.group <= 32 && !o.no_ray_sweep)

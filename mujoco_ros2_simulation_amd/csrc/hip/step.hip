@@ -52,6 +52,10 @@ constexpr int kBuiltSel = MRS_PART_SEL;
 #else
 constexpr int kBuiltSel = kSelAll;
 #endif
+// the fused 16-lane solves (DevModel::solve_fuse) are built into the parts that hold a plain PGS step
+// kernel; the parts of the Newton / CG kernels alone and of the helper-wave kernels alone, whose
+// batches never take them, keep the separate form's code and registers
+constexpr bool kSolveFuseBuilt = (kBuiltSel & (kSelForward | kSelStep)) != 0;
 
 namespace {
 
@@ -1864,8 +1868,9 @@ __device__ __forceinline__ void chol_rows16(const lfloat* A, lfloat* Lf, int nv,
 
 // two factors in one pass: M (into Lf) and M + diag(h dg) (into Lh, which may alias A): the same
 // register row form, the two column chains interleaved so each hides the other's latency
-// (DevModel::fuse_ih); the diagonal update is integrate()'s fma, so both factors are bit-identical to
-// the separate ones
+// (DevModel::fuse_ih); the diagonal update is integrate()'s fma; the fused factor of M + h D still
+// differs from the one integrate() builds by fp32 rounding (<= 1e-4 over a rollout,
+// tests/test_gpu_ray_helpers.py): it is not bit-identical
 template <int N>
 __device__ __forceinline__ void chol_rows16_dual(const lfloat* A, lfloat* Lf, lfloat* Lh, float h, float dg, int nv,
                                                  int lane) {
@@ -1957,15 +1962,39 @@ __device__ MRS_PHASE void cholesky(const DevModel* __restrict__ mp, const lfloat
 // x = A^-1 b with A = Lf Lf'; lane j holds b_j / returns x_j (lanes >= nv return 0)
 // G = 16 solve, N = unroll bound >= nv: lane j prefetches row j of L (forward) and column j
 // (backward); the substitution chains are DPP broadcasts and FMAs
-template <int N>
-__device__ __forceinline__ float chol_solve_rows16(const lfloat* Lf, float x, int nv, int lane) {
+// one_rcp (DevModel::solve_fuse): lane i reads its own L_ii and takes the reciprocal once; the levels
+// take it from that lane by a row broadcast -- the same 1.0f / L_ii, so the same products -- in place of
+// a diagonal read and a reciprocal per level
+// (kMay: the call may take that form; without it the one statement order the solve always had)
+template <int N, bool kMay>
+__device__ __forceinline__ float chol_solve_rows16(const lfloat* Lf, float x, int nv, int lane, bool one_rcp) {
   float lrow[N], lcol[N], inv[N];
-  unroll<N>([&](auto ic) {
-    constexpr int i = decltype(ic)::value;
-    lrow[i] = (i < nv && lane < nv) ? Lf[lane * nv + i] : 0.0f;
-    lcol[i] = (i < nv && lane < nv) ? Lf[i * nv + lane] : 0.0f;
-    inv[i] = i < nv ? 1.0f / Lf[i * nv + i] : 0.0f;
-  });
+  if constexpr (!kMay) {
+    unroll<N>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      lrow[i] = (i < nv && lane < nv) ? Lf[lane * nv + i] : 0.0f;
+      lcol[i] = (i < nv && lane < nv) ? Lf[i * nv + lane] : 0.0f;
+      inv[i] = i < nv ? 1.0f / Lf[i * nv + i] : 0.0f;
+    });
+  } else {
+    unroll<N>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      lrow[i] = (i < nv && lane < nv) ? Lf[lane * nv + i] : 0.0f;
+      lcol[i] = (i < nv && lane < nv) ? Lf[i * nv + lane] : 0.0f;
+    });
+    if (one_rcp) {
+      const float myinv = 1.0f / (lane < nv ? Lf[lane * nv + lane] : 1.0f);
+      unroll<N>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        inv[i] = i < nv ? rowb<i>(myinv) : 0.0f;
+      });
+    } else {
+      unroll<N>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        inv[i] = i < nv ? 1.0f / Lf[i * nv + i] : 0.0f;
+      });
+    }
+  }
   unroll<N>([&](auto ic) {
     constexpr int i = decltype(ic)::value;
     if (i < nv) {
@@ -1983,7 +2012,9 @@ __device__ __forceinline__ float chol_solve_rows16(const lfloat* Lf, float x, in
   return x;
 }
 
-template <int G>
+// kOneRcp: the G = 16 solve may take the one-reciprocal form (DevModel::solve_fuse decides at run time):
+// the smooth-force and integrator solves; the primal solvers' and the dense rows' calls keep one form
+template <int G, bool kOneRcp = false>
 __device__ MRS_PHASE float chol_solve_lanes(const DevModel* __restrict__ mp, const lfloat* Lf, float b, int lane) {
   mp = uniform_ptr(mp);
   if constexpr (G == 64) Lf = uniform_lds(const_cast<lfloat*>(Lf));
@@ -1991,7 +2022,9 @@ __device__ MRS_PHASE float chol_solve_lanes(const DevModel* __restrict__ mp, con
   const int nv = load_model(mp).nv;
   float x = lane < nv ? b : 0.0f;
   if constexpr (G == 16) {
-    x = nv <= 8 ? chol_solve_rows16<8>(Lf, x, nv, lane) : chol_solve_rows16<16>(Lf, x, nv, lane);
+    constexpr bool kMay = kOneRcp && kSolveFuseBuilt;
+    const bool one_rcp = kMay && load_model(mp).solve_fuse != 0;
+    x = nv <= 8 ? chol_solve_rows16<8, kMay>(Lf, x, nv, lane, one_rcp) : chol_solve_rows16<16, kMay>(Lf, x, nv, lane, one_rcp);
     return lane < nv ? x : 0.0f;
   }
   if constexpr (G == 64) {
@@ -2884,9 +2917,11 @@ __device__ void rk4_act(ENV_PARAMS, int stage) {
   wsync();
 }
 
-// mj_passive + mj_fwdActuation + qfrc_smooth + qacc_smooth (lane per dof)
+// mj_passive + mj_fwdActuation + qfrc_smooth + qacc_smooth (lane per dof).  defer (forward(): 16-lane
+// PGS kernels with DevModel::solve_fuse): qacc_smooth is left to constraints(), which solves it with its
+// friction-loss rows or, on the dense path, by the same call as here; the lane's qfrc_smooth is returned
 template <int G>
-__device__ MRS_PHASE float smooth_forces(ENV_PARAMS) {
+__device__ MRS_PHASE float smooth_forces(ENV_PARAMS, bool defer = false) {
   ENV_UNPACK;
   const int nv = m.nv;
   // fixed tendons (mj_tendon): length and velocity of each into the step's tendon slot (lane per tendon)
@@ -2998,8 +3033,12 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS) {
     if (m.xfrc) qfs += qx;
     s[L.qfrc_smooth + j] = qfs;
   }
+  if (defer) {
+    wsync();
+    return qfs;
+  }
   float qacc_s;
-  MRS_CALL(G, qacc_s = chol_solve_lanes<G>(mp, s + L.L, qfs, lane));
+  MRS_CALL(G, qacc_s = (chol_solve_lanes<G, true>)(mp, s + L.L, qfs, lane));
   if (lane < nv) s[L.qacc_smooth + lane] = qacc_s;
   wsync();
   return qacc_s;
@@ -3396,9 +3435,14 @@ __device__ __forceinline__ float pgs_small16(const DevModel& m, lfloat* s, const
 // The same PGS in qacc form (each row's residual is a group sum of J_r qacc): used for the
 // friction-loss unit rows, whose systems converge in a few sweeps, where the dual form's O(rows^2)
 // Delassus set-up costs more than its shorter sweep chain saves (C3: 179 vs 171 M env-steps/s)
-template <bool kUnit = false, int KR = 16>
+// fuse (DevModel::solve_fuse, the friction-loss fast path): qacc_s arrives as qfrc_smooth and is solved
+// here as one more column of the substitution, in chol_solve_rows16's operand order (so qacc_smooth
+// has the bits the separate solve gives); its chain hides under the rows'.  The lane's row and column
+// of L are read in one burst before the levels and 1 / L_ii once, by the diagonal's lane -- no LDS
+// read or reciprocal feeds a level's fma.  The row's myb = qacc_smooth - aref is formed after it.
+template <bool kUnit = false, int KR = 16, bool fuse = false>
 __device__ __forceinline__ float pgs_small16_qacc(const DevModel& m, lfloat* s, const gfloat* J, gfloat* ff, int nefc, int rmax,
-                                             float myR, float myaref, float myb, float myfl, float qacc_s,
+                                             float myR, float myaref, float myb, float myfl, float& qacc_s,
                                              float pscale, int lane, int mydof = -1, unsigned fmask = 0) {
   const LdsLayout& L = m.L;
   const int nv = m.nv;
@@ -3420,34 +3464,83 @@ __device__ __forceinline__ float pgs_small16_qacc(const DevModel& m, lfloat* s, 
     MJt[r] = Jt[r];
   });
   // M^-1 J' for all rows at once: forward then backward substitution with L (Cholesky of M, LDS)
-  unroll<KR>([&](auto ic) {
-    constexpr int i = decltype(ic)::value;
-    if (i < nv) {
-      const float inv = 1.0f / s[L.L + i * nv + i];
-      const float lji = (lane > i && lane < nv) ? s[L.L + lane * nv + i] : 0.0f;
-      unroll<KR>([&](auto rc) {
-        constexpr int r = decltype(rc)::value;
-        if (r < rmax) {
-          const float xi = rowb<i>(MJt[r]) * inv;
-          MJt[r] = lane == i ? xi : MJt[r] - lji * xi;
-        }
-      });
-    }
-  });
-  unroll<KR>([&](auto ic) {
-    constexpr int i = KR - 1 - decltype(ic)::value;
-    if (i < nv) {
-      const float inv = 1.0f / s[L.L + i * nv + i];
-      const float lij = lane < i ? s[L.L + i * nv + lane] : 0.0f;
-      unroll<KR>([&](auto rc) {
-        constexpr int r = decltype(rc)::value;
-        if (r < rmax) {
-          const float zi = rowb<i>(MJt[r]) * inv;
-          MJt[r] = lane == i ? zi : MJt[r] - lij * zi;
-        }
-      });
-    }
-  });
+  if constexpr (fuse) {
+    float lrow[KR], lcol[KR];
+    unroll<KR>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      lrow[i] = (i < nv && lane > i && lane < nv) ? s[L.L + lane * nv + i] : 0.0f;
+    });
+    const float myinv = 1.0f / (lane < nv ? s[L.L + lane * nv + lane] : 1.0f);
+    float x = lane < nv ? qacc_s : 0.0f;  // qfrc_smooth
+    unroll<KR>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      if (i < nv) {
+        const float inv = rowb<i>(myinv);
+        unroll<KR>([&](auto rc) {
+          constexpr int r = decltype(rc)::value;
+          // (kUnit: column r is the unit vector of dof r, still zero in lanes 0..r-1 at the levels
+          // i < r, where xi = 0 and the level leaves every lane as it is: skipped)
+          if (r < rmax && (!kUnit || r <= i)) {
+            const float xi = rowb<i>(MJt[r]) * inv;
+            MJt[r] = lane == i ? xi : MJt[r] - lrow[i] * xi;
+          }
+        });
+        const float xi = rowb<i>(x) * inv;
+        x = lane == i ? xi : (lane > i ? x - lrow[i] * xi : x);
+      }
+    });
+    // (the lane's column in a second burst, once the rows' registers are free)
+    unroll<KR>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      lcol[i] = (i < nv && lane < i) ? s[L.L + i * nv + lane] : 0.0f;
+    });
+    unroll<KR>([&](auto ic) {
+      constexpr int i = KR - 1 - decltype(ic)::value;
+      if (i < nv) {
+        const float inv = rowb<i>(myinv);
+        unroll<KR>([&](auto rc) {
+          constexpr int r = decltype(rc)::value;
+          if (r < rmax) {
+            const float zi = rowb<i>(MJt[r]) * inv;
+            MJt[r] = lane == i ? zi : MJt[r] - lcol[i] * zi;
+          }
+        });
+        const float xi = rowb<i>(x) * inv;
+        x = lane == i ? xi : (lane < i ? x - lcol[i] * xi : x);
+      }
+    });
+    qacc_s = lane < nv ? x : 0.0f;
+    if (myrow) myb = qacc_s - myaref;
+  } else {
+    unroll<KR>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      if (i < nv) {
+        const float inv = 1.0f / s[L.L + i * nv + i];
+        const float lji = (lane > i && lane < nv) ? s[L.L + lane * nv + i] : 0.0f;
+        unroll<KR>([&](auto rc) {
+          constexpr int r = decltype(rc)::value;
+          if (r < rmax) {
+            const float xi = rowb<i>(MJt[r]) * inv;
+            MJt[r] = lane == i ? xi : MJt[r] - lji * xi;
+          }
+        });
+      }
+    });
+    unroll<KR>([&](auto ic) {
+      constexpr int i = KR - 1 - decltype(ic)::value;
+      if (i < nv) {
+        const float inv = 1.0f / s[L.L + i * nv + i];
+        const float lij = lane < i ? s[L.L + i * nv + lane] : 0.0f;
+        unroll<KR>([&](auto rc) {
+          constexpr int r = decltype(rc)::value;
+          if (r < rmax) {
+            const float zi = rowb<i>(MJt[r]) * inv;
+            MJt[r] = lane == i ? zi : MJt[r] - lij * zi;
+          }
+        });
+      }
+    });
+  }
   float myA = 1, myf = 0;  // lane r: A_rr = J_r M^-1 J_r' + R_r and the force of row r
   unroll<KR>([&](auto rc) {
     constexpr int r = decltype(rc)::value;
@@ -5806,8 +5899,27 @@ __device__ float constraints_dense(ENV_PARAMS, int ncon, float qacc_s, int pre_n
 template <int G>
 __device__ int dense_rows(ENV_PARAMS, int ncon);
 
+// the friction-loss fast path of constraints<16> with qacc_smooth already solved: pgs_small16_qacc in its
+// separate form (a divide and two LDS reads per level), a function of its own (a template, so that only
+// the parts that call it hold it)
+template <int G>
+__device__ float pgs_unit_separate(ENV_PARAMS, int nf, float myR, float myaref, float myb, float myfl, float qacc_s,
+                                   int myk, unsigned fmask) {
+  ENV_UNPACK;
+  float qa;
+  if (m.nv <= 8)
+    qa = pgs_small16_qacc<true, 8>(m, s, nullptr, scr + S.efc_f, nf, 8, myR, myaref, myb, myfl, qacc_s, solver_scale(m, scr), lane, myk, fmask);
+  else
+    qa = pgs_small16_qacc<true, 16>(m, s, nullptr, scr + S.efc_f, nf, 16, myR, myaref, myb, myfl, qacc_s, solver_scale(m, scr), lane, myk, fmask);
+  wsync();
+  return qa;
+}
+
+// smooth_deferred (forward(), smooth_forces): qacc_s arrives as the lane's qfrc_smooth and qacc_smooth is
+// solved and stored here -- by the friction-loss fast path as a column of its own substitution, before
+// the dense path by the solve smooth_forces would have run
 template <int G, bool kPrimal = false, bool kHot = false>
-__device__ MRS_PHASE float constraints(ENV_PARAMS, int ncon, float qacc_s, int pre_nefc = -1) {
+__device__ MRS_PHASE float constraints(ENV_PARAMS, int ncon, float qacc_s, int pre_nefc = -1, bool smooth_deferred = false) {
   ENV_UNPACK;
   if constexpr (G == 64) {
     if (m.solver != MRS_SOL_PGS || m.cone == MRS_CONE_ELLIPTIC || m.xrows > 0) {
@@ -5868,7 +5980,7 @@ __device__ MRS_PHASE float constraints(ENV_PARAMS, int ncon, float qacc_s, int p
           const lfloat* fr = shared_lds(m) + m.shr_fric + 4 * myk;
           myR = fric_R_env(m, scr, myk, fr[1]);
           myaref = -fr[2] * s[L.qvel + lane];  // friction rows have no position term
-          myb = s[L.qacc_smooth + lane] - myaref;
+          if (!smooth_deferred) myb = s[L.qacc_smooth + lane] - myaref;  // (deferred: pgs_small16_qacc forms it)
           myfl = fr[3];
         }
       }
@@ -5885,13 +5997,35 @@ __device__ MRS_PHASE float constraints(ENV_PARAMS, int ncon, float qacc_s, int p
         return qa;
       }
       // dofs unrolled to 8 when the model has at most 8: a quarter of the substitution code
+      if constexpr (!kSolveFuseBuilt) {
+        // (the parts of the helper-wave kernels alone: the separate form inline, as it always was)
+        if (m.nv <= 8)
+          qa = pgs_small16_qacc<true, 8>(m, s, nullptr, scr + S.efc_f, nf, 8, myR, myaref, myb, myfl, qacc_s, solver_scale(m, scr), lane, myk, fmask);
+        else
+          qa = pgs_small16_qacc<true, 16>(m, s, nullptr, scr + S.efc_f, nf, 16, myR, myaref, myb, myfl, qacc_s, solver_scale(m, scr), lane, myk, fmask);
+        wsync();
+        return qa;
+      }
+      if (!smooth_deferred) {
+        // the separate form where the fused one is built (qacc_smooth solved by smooth_forces:
+        // MRS_NO_SOLVE_FUSE=1, helper waves): out of line, so that the step loop's code holds one form
+        [[clang::noinline]] qa = pgs_unit_separate<G>(ENV_ARGS, nf, myR, myaref, myb, myfl, qacc_s, myk, fmask);
+        return qa;
+      }
       if (m.nv <= 8)
-        qa = pgs_small16_qacc<true, 8>(m, s, nullptr, scr + S.efc_f, nf, 8, myR, myaref, myb, myfl, qacc_s, solver_scale(m, scr), lane, myk, fmask);
+        qa = pgs_small16_qacc<true, 8, true>(m, s, nullptr, scr + S.efc_f, nf, 8, myR, myaref, myb, myfl, qacc_s, solver_scale(m, scr), lane, myk, fmask);
       else
-        qa = pgs_small16_qacc<true, 16>(m, s, nullptr, scr + S.efc_f, nf, 16, myR, myaref, myb, myfl, qacc_s, solver_scale(m, scr), lane, myk, fmask);
+        qa = pgs_small16_qacc<true, 16, true>(m, s, nullptr, scr + S.efc_f, nf, 16, myR, myaref, myb, myfl, qacc_s, solver_scale(m, scr), lane, myk, fmask);
+      if (lane < nv) s[L.qacc_smooth + lane] = qacc_s;
       wsync();
       return qa;
     }
+  }
+  if (kSolveFuseBuilt && smooth_deferred) {
+    const float qfs = qacc_s;
+    MRS_CALL(G, qacc_s = (chol_solve_lanes<G, true>)(mp, s + L.L, qfs, lane));
+    if (lane < nv) s[L.qacc_smooth + lane] = qacc_s;
+    wsync();
   }
   // rows with contacts or active joint limits: the dense row path, out of line -- cold in C3's
   // steady state, and keeping it out of the inlined step loop keeps the hot code footprint small
@@ -7806,8 +7940,13 @@ __device__ MRS_PHASE int forward(ENV_PARAMS, gfloat* sensordata, bool sens PH_AC
   PH_END(ph_acc, PH_COMVEL);
   MRS_CALL(G, rne<G>(ENV_ARGS));
   PH_END(ph_acc, PH_RNE);
-  float qacc_s;
-  MRS_CALL(G, qacc_s = smooth_forces<G>(ENV_ARGS));
+  // 16-lane PGS kernels: qacc_smooth is solved in constraints(), with the friction-loss rows where the
+  // step takes that path (DevModel::solve_fuse; not beside helper waves, whose row set-up reads it, nor
+  // where constraints() does not run or returns at once)
+  const bool defer_smooth = kSolveFuseBuilt && G == 16 && !kPrimal && m.solve_fuse && m.solver == MRS_SOL_PGS && !helper &&
+                            !(m.diag_skip & 4) && !(m.disableflags & MRS_DSBL_CONSTRAINT);
+  float qacc_s;  // (deferred: qfrc_smooth until constraints() has solved it)
+  MRS_CALL(G, qacc_s = smooth_forces<G>(ENV_ARGS, defer_smooth));
   PH_END(ph_acc, PH_SMOOTH);
   int ncon = 0, pre_nefc = -1;
   if (helper) {
@@ -7827,7 +7966,7 @@ __device__ MRS_PHASE int forward(ENV_PARAMS, gfloat* sensordata, bool sens PH_AC
     // no rows unless constraints() builds some (mrs_batch_get_efc), or the helper's
     scr[S.efc_n] = __int_as_float(pre_nefc >= 0 ? pre_nefc : 0);
   }
-  if (!(m.diag_skip & 4)) MRS_CALL(G, qacc = (constraints<G, kPrimal, kHot>(ENV_ARGS, ncon, qacc_s, pre_nefc)));
+  if (!(m.diag_skip & 4)) MRS_CALL(G, qacc = (constraints<G, kPrimal, kHot>(ENV_ARGS, ncon, qacc_s, pre_nefc, defer_smooth)));
   PH_END(ph_acc, PH_CONSTR);
   if (lane < m.nv) s[L.qacc + lane] = qacc;
   if (acc_bad) *acc_bad = gany<G>(lane < m.nv && is_bad(qacc));
@@ -7979,13 +8118,13 @@ __device__ MRS_PHASE void integrate(ENV_PARAMS, bool prefac = false) {
   if (need_solve) {
     const float rhs = lane < nv ? s[L.qfrc_smooth + lane] + s[L.qfrc_con + lane] : 0.0f;
     if (prefac) {
-      MRS_CALL(G, qacc_int = chol_solve_lanes<G>(mp, s + (m.fuse_ih && m.solver == MRS_SOL_PGS ? L.M : L.Lh), rhs, lane));
+      MRS_CALL(G, qacc_int = (chol_solve_lanes<G, true>)(mp, s + (m.fuse_ih && m.solver == MRS_SOL_PGS ? L.M : L.Lh), rhs, lane));
     } else {
       // M + h*diag(dg) into the M slot (M is rebuilt every step), factor into L
       if (lane < nv) s[L.M + midx<G>(m, lane, lane)] += h * dg;
       wsync();
       MRS_CALL(G, cholesky<G>(mp, s + L.M, s + L.L, lane));
-      MRS_CALL(G, qacc_int = chol_solve_lanes<G>(mp, s + L.L, rhs, lane));
+      MRS_CALL(G, qacc_int = (chol_solve_lanes<G, true>)(mp, s + L.L, rhs, lane));
     }
   }
   if (lane < nv) {

@@ -433,6 +433,8 @@ LAYOUT_KEYS = ["group", "lds_floats", "scratch_floats", "blocked", "pipe_w", "ma
 LAYOUT_OUTPUT_KEYS = ["contact_wrench"]
 # and after those: the dynamics outputs that are on, a bit mask (1 << DYNOUT_*)
 LAYOUT_DYN_KEYS = ["dyn_outputs"]
+# and last: 1 when the 16-lane solves are fused (0 otherwise, and under MRS_NO_SOLVE_FUSE=1)
+LAYOUT_SOLVE_KEYS = ["solve_fuse"]
 
 
 def plan_layout(model: "Model", n_envs: int, cu_count: int, max_contacts: int = 0) -> dict:
@@ -640,7 +642,7 @@ class Batch:
     def layout(self) -> dict:
         """kernel configuration of this batch (diagnostics): group width, LDS and scratch floats per
         env, blocked mode, pipe width, row and contact capacity, kinematic trees"""
-        keys = LAYOUT_KEYS + LAYOUT_OUTPUT_KEYS + LAYOUT_DYN_KEYS
+        keys = LAYOUT_KEYS + LAYOUT_OUTPUT_KEYS + LAYOUT_DYN_KEYS + LAYOUT_SOLVE_KEYS
         out = np.zeros(len(keys), dtype=np.int32)
         k = lib().mrs_debug_batch_layout(self._h, out.ctypes.data, len(keys))
         return dict(zip(keys[:k], out[:k].tolist()))
