@@ -297,6 +297,58 @@ int mrs_batch_render_async(mrs_batch* b, int cam, int env0, int n, float* d_dept
 /* order the batch stream after the last asynchronous render (its frames are complete for any work
  * queued on the batch stream afterwards; mrs_batch_sync also waits for it) */
 int mrs_batch_render_wait(mrs_batch* b);
+
+/* ---- batched ray queries against the posed scene: mj_ray / mj_multiRay for every env (the reference's
+ * lidar is built on mj_ray, src/mujoco_lidar.cpp).  Height scanners, lidar patterns and line-of-sight
+ * tests need no <rangefinder> per ray, and the rays may change from one call to the next. */
+enum {
+  MRS_RAY_SHARED = 1,    /* flags: pnt / vec are one pattern [n_rays][3] for every env */
+  MRS_RAY_NO_STATIC = 2  /* flags: drop the geoms of bodies welded to the world (mj_ray flg_static = 0) */
+};
+enum {
+  MRS_RAY_FRAME_WORLD = 0,  /* pnt / vec are world coordinates; frame_id is ignored */
+  MRS_RAY_FRAME_GEOM = 1,   /* in geom frame_id's frame: each env's own pose of that geom */
+  MRS_RAY_FRAME_CAMERA = 2  /* in camera frame_id's frame, likewise */
+};
+/* Rays: d_pnt and d_vec are device fp32 [n_envs][n_rays][3], with MRS_RAY_SHARED [n_rays][3]; outputs
+ * d_dist fp32 and d_geomid int32 (may be NULL) are [n_envs][n_rays].  As in mj_ray, vec need not be
+ * normalised and dist is in units of |vec|; a miss gives dist -1 and geomid -1.  A zero vec (or one whose
+ * squared length is not a positive finite fp32 number) is a miss, never a NaN.  The nearest hit wins; equal
+ * distances go to the lower geom id.  n_rays == 0 succeeds without a launch (the pointers are not looked at).
+ *
+ * Frames are the poses the device already holds: the world, a geom or a camera.  A pattern mounted on a
+ * site or body is the caller's to build: read MRS_DYNOUT_SITE_POSE on the device and pass per-env world
+ * rays.
+ *
+ * Filters, with mj_ray's meaning: group_mask bit g (0..5) keeps the geoms of group g, 0 keeps every group
+ * (geomgroup == NULL), and with a mask a geom whose group is outside 0..5 is dropped; MRS_RAY_NO_STATIC
+ * drops the geoms of bodies with body_weldid == 0 (the world's and those welded to it, mocap bodies
+ * included); bodyexclude drops one body's geoms (-1: none); geoms with rgba alpha exactly 0 are always
+ * dropped.  Height fields are never hit.
+ *
+ * Which poses: those of the last mrs_batch_step / mrs_batch_forward, as mj_ray reads mjData.  After
+ * mrs_batch_step(b, n) they belong to the last step's forward pass, i.e. the state BEFORE that step's
+ * integration; a caller who wants them at the current qpos calls mrs_batch_forward first.  Before any
+ * step or forward the call reads the pose buffers as they are, as mrs_batch_render_depth does: batch
+ * creation runs one forward, so they hold the poses at qpos0, and a reset or a qpos write does not
+ * move them.
+ *
+ * Asynchronous on the batch stream, no synchronisation: stream order alone places the query after the
+ * launches queued before.  The first query with a new (group_mask, NO_STATIC, bodyexclude) triple uploads
+ * that filter's geom list (a short synchronising copy); the batch keeps the last few, so a repeated query
+ * does no host work beyond the launch.
+ * MRS_ERR_INVALID, before any launch, for a null handle, a null d_pnt / d_vec / d_dist, negative n_rays, an
+ * unknown flag or frame type, frame_id outside the geoms / cameras, bodyexclude outside [-1, nbody). */
+int mrs_batch_ray_device(mrs_batch* b, const float* d_pnt, const float* d_vec, int n_rays, int flags,
+                         int frame_type, int frame_id, unsigned group_mask, int bodyexclude,
+                         float* d_dist, int* d_geomid);
+/* same with host fp64 arrays for envs [env0, env0 + n): pnt / vec [n][n_rays][3] (or [n_rays][3] shared),
+ * dist and geomid (may be NULL) [n][n_rays].  Stages the rays (through fp32, as mrs_batch_set_field
+ * converts), launches and synchronises.  Also MRS_ERR_INVALID for an env range outside the batch; n == 0
+ * succeeds without a launch. */
+int mrs_batch_ray(mrs_batch* b, const double* pnt, const double* vec, int n_rays, int flags,
+                  int frame_type, int frame_id, unsigned group_mask, int bodyexclude,
+                  double* dist, int* geomid, int env0, int n);
 /* mjData.contact of env `env` after its last step / forward (the output of mj_collision, SURVEY.md
  * §8a row a2.3): up to `max` contacts in mj_collision's order -- geom [max][2] int32 (geom1, geom2,
  * the lower geom type first), dist [max], pos [max][3], frame [max][9] fp64 (normal = frame[0:3]);
@@ -421,6 +473,12 @@ int mrs_debug_batch_layout(const mrs_batch* b, int* out, int n);
  * the plan chosen, nothing else.  Returns the number of values written, MRS_ERR_INVALID for a null or
  * bad argument, MRS_ERR_UNSUPPORTED for a model mrs_batch_create refuses with it. */
 int mrs_debug_plan_layout(const mrs_model* m, int n_envs, int cu_count, int max_contacts, int* out, int n);
+/* diagnostics: the ids of the geoms a ray query with this group_mask, flags (MRS_RAY_NO_STATIC; MRS_RAY_SHARED
+ * is accepted and ignored) and bodyexclude may hit, in geom order -- the list the batch uploads for the
+ * query kernel.  Up to `max` ids are written to out (may be NULL when max == 0); returns the count, which
+ * may exceed `max`, or MRS_ERR_INVALID for a null model, an unknown flag or a bodyexclude outside
+ * [-1, nbody).  No device needed. */
+int mrs_debug_ray_filter(const mrs_model* m, unsigned group_mask, int flags, int bodyexclude, int* out, int max);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@
 #include "../../include/mrs.h"
 #include "hip/batch.h"
 #include "mjcf/model.h"
+#include "hip/rayfilter.h"
 #include "hip/start_rows.h"
 #include "mjcf/xml.h"
 
@@ -444,6 +445,24 @@ int mrs_batch_render_wait(mrs_batch* b) {
   });
 }
 
+int mrs_batch_ray_device(mrs_batch* b, const float* d_pnt, const float* d_vec, int n_rays, int flags, int frame_type,
+                         int frame_id, unsigned group_mask, int bodyexclude, float* d_dist, int* d_geomid) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_ray_device(b->impl, d_pnt, d_vec, n_rays, flags, frame_type, frame_id, group_mask, bodyexclude, d_dist,
+                          d_geomid);
+  });
+}
+
+int mrs_batch_ray(mrs_batch* b, const double* pnt, const double* vec, int n_rays, int flags, int frame_type,
+                  int frame_id, unsigned group_mask, int bodyexclude, double* dist, int* geomid, int env0, int n) {
+  return guarded([&] {
+    if (!b) throw std::invalid_argument("null batch");
+    mrs::batch_ray(b->impl, pnt, vec, n_rays, flags, frame_type, frame_id, group_mask, bodyexclude, dist, geomid, env0,
+                   n);
+  });
+}
+
 int mrs_batch_get_contacts(mrs_batch* b, int env, int max, int* geom, double* dist, double* pos, double* frame) {
   int ncon = 0;
   const int rc = guarded([&] {
@@ -568,6 +587,20 @@ int mrs_debug_plan_layout(const mrs_model* m, int n_envs, int cu_count, int max_
     if (!m || !out || n < 0) throw std::invalid_argument("null model or output");
     if (n_envs < 1) throw std::invalid_argument("n_envs must be positive");
     k = mrs::plan_layout(m->m, n_envs, cu_count, max_contacts, out, n);
+  });
+  return rc == MRS_OK ? k : rc;
+}
+
+int mrs_debug_ray_filter(const mrs_model* m, unsigned group_mask, int flags, int bodyexclude, int* out, int max) {
+  int k = 0;
+  const int rc = guarded([&] {
+    if (!m) throw std::invalid_argument("null model");
+    if (max < 0 || (max > 0 && !out)) throw std::invalid_argument("null output or negative capacity");
+    mrs::check_ray_filter(m->m, flags, bodyexclude);
+    const std::vector<mrs::RayGeom> list =
+        mrs::build_ray_filter(m->m, group_mask, (flags & MRS_RAY_NO_STATIC) != 0, bodyexclude);
+    k = static_cast<int>(list.size());
+    for (int i = 0; i < k && i < max; ++i) out[i] = list[i].id;
   });
   return rc == MRS_OK ? k : rc;
 }

@@ -59,6 +59,13 @@ void batch_launch(BatchImpl* b, int n_steps, bool forward_only);
 void batch_render_depth(BatchImpl* b, int cam, int env0, int n, float* out, bool device_out, unsigned char* rgb = nullptr);
 void batch_render_async(BatchImpl* b, int cam, int env0, int n, float* d_out, unsigned char* d_rgb);
 void batch_render_wait(BatchImpl* b);
+// ray queries against the poses of the last step / forward (mrs.h MRS_RAY_*): device rays and outputs for
+// every env, asynchronous on the batch stream, and host fp64 rows for envs [env0, env0 + n), synchronised;
+// geomid may be null.  Every argument is checked before any launch
+void batch_ray_device(BatchImpl* b, const float* d_pnt, const float* d_vec, int n_rays, int flags, int frame_type,
+                      int frame_id, unsigned group_mask, int bodyexclude, float* d_dist, int* d_geomid);
+void batch_ray(BatchImpl* b, const double* pnt, const double* vec, int n_rays, int flags, int frame_type, int frame_id,
+               unsigned group_mask, int bodyexclude, double* dist, int* geomid, int env0, int n);
 int batch_get_contacts(BatchImpl* b, int env, int max, int* geom, double* dist, double* pos, double* frame);
 int batch_get_efc(BatchImpl* b, int env, int max, int* type, double* J, double* R, double* aref, double* force);
 // mj_contactForce per contact of batch_get_contacts' list ([max][6], contact frame; returns ncon), and the

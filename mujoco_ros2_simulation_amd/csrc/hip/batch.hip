@@ -23,6 +23,7 @@
 #include "devtables.h"
 #include "plan.h"
 #include "raymesh.h"
+#include "rayfilter.h"
 #include "lit.h"
 #include "start_rows.h"
 
@@ -135,6 +136,7 @@ __device__ float ray_prim(int type, const float* s, const float lp[3], const flo
   return -1;
 }
 
+#include "rayquery.h"
 
 // ---- colour: the lit model of lit.h (oracle.c lit_color restates it in fp64); local_normal gives
 // the geom-frame surface normal (unnormalised) at a hit point p
@@ -996,6 +998,9 @@ struct BatchImpl {
   unsigned long long* rast_list = nullptr;
   int rast_frames = 0;
   int max_lds = 0;  // hipDeviceAttributeMaxSharedMemoryPerBlock of the batch's device
+  // ray queries (batch_ray): the uploaded geom lists of the filter triples seen so far, oldest first
+  struct RayList { unsigned group_mask; bool no_static; int bodyexclude; RayGeom* d; int count; bool mesh; };
+  std::deque<RayList> ray_lists;
   // the model needs the extended step kernels (step.hip MRS_EXT): general convex (MPR) collision
   // pairs, or rangefinders with more than 32 ray geoms
   bool ext = false;
@@ -1419,6 +1424,7 @@ void batch_free(BatchImpl* b) {
   if (b->pool_qpos) (void)hipFree(b->pool_qpos);
   if (b->pool_qvel) (void)hipFree(b->pool_qvel);
   if (b->rast_list) (void)hipFree(b->rast_list);
+  for (const BatchImpl::RayList& l : b->ray_lists) (void)hipFree(l.d);
   if (b->snap_ev) (void)hipEventDestroy(b->snap_ev);
   if (b->rend_ev) (void)hipEventDestroy(b->rend_ev);
   if (b->rstream) (void)hipStreamDestroy(b->rstream);
@@ -1920,6 +1926,129 @@ void batch_render_async(BatchImpl* b, int cam, int env0, int n, float* d_out, un
 void batch_render_wait(BatchImpl* b) {
   HIP_CHECK(hipSetDevice(b->device));
   if (b->rend_pending) HIP_CHECK(hipStreamWaitEvent(b->stream, b->rend_ev, 0));
+}
+
+// ---- ray queries (mrs_batch_ray / mrs_batch_ray_device; kernel: rayquery.h, geom lists: rayfilter.h)
+namespace {
+constexpr size_t kRayListCache = 8;
+
+// the device list of a filter triple: uploaded on first use and kept, the oldest of kRayListCache dropped
+// for a new one (after the queued queries that may read it have run)
+const BatchImpl::RayList& ray_list(BatchImpl* b, unsigned group_mask, bool no_static, int bodyexclude) {
+  for (const BatchImpl::RayList& l : b->ray_lists)
+    if (l.group_mask == group_mask && l.no_static == no_static && l.bodyexclude == bodyexclude) return l;
+  const std::vector<RayGeom> host = build_ray_filter(*b->model, group_mask, no_static, bodyexclude);
+  if (b->ray_lists.size() >= kRayListCache) {
+    HIP_CHECK(hipStreamSynchronize(b->stream));
+    HIP_CHECK(hipFree(b->ray_lists.front().d));
+    b->ray_lists.pop_front();
+  }
+  BatchImpl::RayList l{group_mask, no_static, bodyexclude, nullptr, static_cast<int>(host.size()),
+                       std::any_of(host.begin(), host.end(), [](const RayGeom& g) { return g.type == MRS_GEOM_MESH; })};
+  HIP_CHECK(hipMalloc(&l.d, std::max<size_t>(1, host.size()) * sizeof(RayGeom)));
+  try {
+    if (!host.empty()) {
+      HIP_CHECK(hipMemcpyAsync(l.d, host.data(), host.size() * sizeof(RayGeom), hipMemcpyHostToDevice, b->stream));
+      HIP_CHECK(hipStreamSynchronize(b->stream));  // (the host list is read by then)
+    }
+  } catch (...) {  // (a list that was never filled is not kept)
+    (void)hipFree(l.d);
+    throw;
+  }
+  b->ray_lists.push_back(l);
+  return b->ray_lists.back();
+}
+
+// every argument of a query that the host can check, before any launch
+void check_ray_args(const BatchImpl* b, int n_rays, int flags, int frame_type, int frame_id, int bodyexclude,
+                    int env0, int n) {
+  const Model& m = *b->model;
+  if (n_rays < 0) throw std::invalid_argument("negative number of rays");
+  check_ray_filter(m, flags, bodyexclude);
+  if (frame_type != MRS_RAY_FRAME_WORLD && frame_type != MRS_RAY_FRAME_GEOM && frame_type != MRS_RAY_FRAME_CAMERA)
+    throw std::invalid_argument("unknown ray frame type");
+  if (frame_type == MRS_RAY_FRAME_GEOM && (frame_id < 0 || frame_id >= m.ngeom))
+    throw std::invalid_argument("ray frame geom out of range");
+  if (frame_type == MRS_RAY_FRAME_CAMERA && (frame_id < 0 || frame_id >= m.ncam))
+    throw std::invalid_argument("ray frame camera out of range");
+  check_env_range(*b, env0, n);
+}
+
+// the launch for envs [env0, env0 + n): device rays and outputs, rows of env0 first; arguments checked
+void ray_launch(BatchImpl* b, const float* d_pnt, const float* d_vec, int n_rays, int flags, int frame_type,
+                int frame_id, unsigned group_mask, int bodyexclude, float* d_dist, int* d_geomid, int env0, int n) {
+  const Model& m = *b->model;
+  const BatchImpl::RayList& l = ray_list(b, group_mask, (flags & MRS_RAY_NO_STATIC) != 0, bodyexclude);
+  RayQueryArgs a{};
+  a.list = l.d; a.nkeep = l.count; a.ngeom = m.ngeom;
+  a.geom_xpos = b->st.geom_xpos; a.geom_xmat = b->st.geom_xmat;
+  if (frame_type == MRS_RAY_FRAME_GEOM) {
+    a.frame_pos = b->st.geom_xpos + 3 * static_cast<size_t>(frame_id);
+    a.frame_mat = b->st.geom_xmat + 9 * static_cast<size_t>(frame_id);
+    a.frame_stride = m.ngeom;
+  } else if (frame_type == MRS_RAY_FRAME_CAMERA) {
+    a.frame_pos = b->st.cam_xpos + 3 * static_cast<size_t>(frame_id);
+    a.frame_mat = b->st.cam_xmat + 9 * static_cast<size_t>(frame_id);
+    a.frame_stride = m.ncam;
+  }
+  a.n_rays = n_rays; a.shared = (flags & MRS_RAY_SHARED) != 0;
+  const DevModel& d = b->dm;
+  const MeshRef mesh{d.mesh_vert.p, d.mesh_face.p, d.geom_dataid.p, d.mesh_vertadr.p, d.mesh_faceadr.p,
+                     d.mesh_facenum.p, d.mesh_bvh.p, d.mesh_bvhadr.p, d.mesh_bvhnum.p, d.mesh_tri.p};
+  const unsigned tiles = static_cast<unsigned>((n_rays + 255) / 256);
+  constexpr int kMaxGridY = 65535;
+  for (int r0 = 0; r0 < n; r0 += kMaxGridY) {  // (the grid's y extent is 16 bits)
+    const int nr = std::min(kMaxGridY, n - r0);
+    const size_t rows = static_cast<size_t>(r0) * n_rays;
+    a.env0 = env0 + r0;
+    a.pnt = d_pnt + (a.shared ? 0 : rows * 3);
+    a.vec = d_vec + (a.shared ? 0 : rows * 3);
+    a.dist = d_dist + rows;
+    a.geomid = d_geomid ? d_geomid + rows : nullptr;
+    hipLaunchKernelGGL(l.mesh ? ray_query_kernel<true> : ray_query_kernel<false>, dim3(tiles, nr), dim3(256), 0,
+                       b->stream, a, mesh);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+}  // namespace
+
+void batch_ray_device(BatchImpl* b, const float* d_pnt, const float* d_vec, int n_rays, int flags, int frame_type,
+                      int frame_id, unsigned group_mask, int bodyexclude, float* d_dist, int* d_geomid) {
+  check_ray_args(b, n_rays, flags, frame_type, frame_id, bodyexclude, 0, b->n);
+  if (n_rays == 0) return;
+  if (!d_pnt || !d_vec || !d_dist) throw std::invalid_argument("null ray or distance buffer");
+  HIP_CHECK(hipSetDevice(b->device));
+  ray_launch(b, d_pnt, d_vec, n_rays, flags, frame_type, frame_id, group_mask, bodyexclude, d_dist, d_geomid, 0, b->n);
+}
+
+void batch_ray(BatchImpl* b, const double* pnt, const double* vec, int n_rays, int flags, int frame_type, int frame_id,
+               unsigned group_mask, int bodyexclude, double* dist, int* geomid, int env0, int n) {
+  check_ray_args(b, n_rays, flags, frame_type, frame_id, bodyexclude, env0, n);
+  if (n_rays == 0 || n == 0) return;
+  if (!pnt || !vec || !dist) throw std::invalid_argument("null ray or distance buffer");
+  HIP_CHECK(hipSetDevice(b->device));
+  // rays through fp32 as rows_to_device converts, distances back as rows_to_host does
+  const size_t nin = static_cast<size_t>((flags & MRS_RAY_SHARED) ? 1 : n) * n_rays * 3;
+  const size_t nout = static_cast<size_t>(n) * n_rays;
+  std::vector<float> in(2 * nin), out(nout);
+  for (size_t k = 0; k < nin; ++k) { in[k] = static_cast<float>(pnt[k]); in[nin + k] = static_cast<float>(vec[k]); }
+  void* tmp = nullptr;
+  HIP_CHECK(hipMallocAsync(&tmp, (2 * nin + 2 * nout) * sizeof(float), b->stream));
+  float* d_in = static_cast<float*>(tmp);
+  float* d_dist = d_in + 2 * nin;
+  int* d_geomid = geomid ? reinterpret_cast<int*>(d_dist + nout) : nullptr;
+  try {
+    HIP_CHECK(hipMemcpyAsync(d_in, in.data(), in.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    ray_launch(b, d_in, d_in + nin, n_rays, flags, frame_type, frame_id, group_mask, bodyexclude, d_dist, d_geomid, env0, n);
+    HIP_CHECK(hipMemcpyAsync(out.data(), d_dist, nout * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    if (geomid) HIP_CHECK(hipMemcpyAsync(geomid, d_geomid, nout * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+  } catch (...) {
+    (void)hipFreeAsync(tmp, b->stream);
+    throw;
+  }
+  HIP_CHECK(hipFreeAsync(tmp, b->stream));
+  HIP_CHECK(hipStreamSynchronize(b->stream));
+  for (size_t k = 0; k < nout; ++k) dist[k] = out[k];
 }
 
 // mjData.efc_* of the last forward pass of one env (type, dense J rows, R, aref, force).  Returns

@@ -44,6 +44,10 @@ PARAM_ACT_GAINPRM, PARAM_ACT_BIASPRM, PARAM_DOF_DAMPING, PARAM_GEOM_FRICTION = r
 # the actuator dyntypes below
 DYNOUT_QFRC_BIAS, DYNOUT_MASS_MATRIX, DYNOUT_SITE_JAC, DYNOUT_SITE_POSE, DYNOUT_COUNT = 0, 1, 2, 3, 4
 MAX_JAC_SITES = 16
+# ray queries (MRS_RAY_*; Batch.ray / ray_device): flags, then frame types
+RAY_SHARED, RAY_NO_STATIC = 1, 2
+RAY_FRAME_WORLD, RAY_FRAME_GEOM, RAY_FRAME_CAMERA = 0, 1, 2
+_RAY_FRAMES = {"world": RAY_FRAME_WORLD, "geom": RAY_FRAME_GEOM, "camera": RAY_FRAME_CAMERA}
 # ActuatorType (include/mujoco_ros2_control/data.hpp:43-51 numbering)
 ACT_UNKNOWN, ACT_MOTOR, ACT_POSITION, ACT_VELOCITY, ACT_CUSTOM = range(5)
 
@@ -286,6 +290,12 @@ def lib() -> C.CDLL:
             L.mrs_batch_dyn_device_ptr.restype = C.c_void_p
             L.mrs_batch_dyn_device_ptr.argtypes = [C.c_void_p, C.c_int]
             L.mrs_batch_get_dyn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
+        if hasattr(L, "mrs_batch_ray"):  # (likewise)
+            L.mrs_batch_ray_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
+            L.mrs_batch_ray.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_uint, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+            L.mrs_debug_ray_filter.argtypes = [C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.mrs_batch_get_field_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
         L.mrs_batch_last_kernel_ms.restype = C.c_double
         L.mrs_batch_last_kernel_ms.argtypes = [C.c_void_p, C.c_int]
@@ -445,6 +455,25 @@ def plan_layout(model: "Model", n_envs: int, cu_count: int, max_contacts: int = 
     if k < 0:
         raise MrsError(k, lib().mrs_last_error().decode())
     return dict(zip(LAYOUT_KEYS[:k], out[:k].tolist()))
+
+
+def ray_filter(model: "Model", group_mask: int = 0, include_static: bool = True, bodyexclude: int = -1) -> np.ndarray:
+    """the ids of the geoms a ray query with these filters may hit, in geom order (mrs_debug_ray_filter):
+    needs no GPU"""
+    out = np.zeros(max(1, model.ngeom), dtype=np.int32)
+    k = lib().mrs_debug_ray_filter(model.handle, group_mask, 0 if include_static else RAY_NO_STATIC, bodyexclude,
+                                   out.ctypes.data, model.ngeom)
+    if k < 0:
+        raise MrsError(k, lib().mrs_last_error().decode())
+    return out[:k].copy()
+
+
+def _ray_args(frame, shared: bool, include_static: bool) -> tuple[int, int, int]:
+    """(flags, frame_type, frame_id) of Batch.ray's keyword arguments"""
+    kind, fid = frame
+    if kind not in _RAY_FRAMES:
+        raise ValueError(f"frame must be one of {sorted(_RAY_FRAMES)}, not {kind!r}")
+    return (RAY_SHARED if shared else 0) | (0 if include_static else RAY_NO_STATIC), _RAY_FRAMES[kind], int(fid)
 
 
 class Batch:
@@ -698,6 +727,45 @@ class Batch:
     def render_wait(self) -> None:
         """order the batch stream after the last asynchronous render"""
         _check(lib().mrs_batch_render_wait(self._h))
+
+    def ray(self, pnt, vec, *, shared: bool | None = None, frame=("world", 0), group_mask: int = 0,
+            include_static: bool = True, bodyexclude: int = -1, env0: int = 0, n: int | None = None,
+            want_geomid: bool = True) -> tuple[np.ndarray, np.ndarray | None]:
+        """mj_ray for every ray of envs [env0, env0 + n): pnt / vec [n, n_rays, 3], or one pattern
+        [n_rays, 3] for every env (shared; the default when pnt has two dimensions), in the world's frame or
+        in frame ("geom" | "camera", id): each env's own pose of it.  Returns (dist [n, n_rays] in units of
+        |vec|, -1 on a miss; geomid [n, n_rays] int32, -1 on a miss, or None without want_geomid).  The
+        poses are those of the last step / forward: after step() the state before the last step's
+        integration; call forward() first for the current qpos.  group_mask bit g keeps group g (0: every
+        group), include_static=False drops the geoms of bodies welded to the world, bodyexclude one body's"""
+        p = np.ascontiguousarray(pnt, dtype=np.float64)
+        v = np.ascontiguousarray(vec, dtype=np.float64)
+        if shared is None:
+            shared = p.ndim == 2
+        n = self.n - env0 if n is None else n
+        ok = p.shape == v.shape and p.shape[-1:] == (3,) and (p.ndim == 2 if shared else p.ndim == 3 and p.shape[0] == n)
+        if not ok:
+            raise ValueError(f"pnt {p.shape} and vec {v.shape} must both be "
+                             f"{'[n_rays, 3]' if shared else f'[{n}, n_rays, 3]'}")
+        n_rays = p.shape[-2]
+        flags, ftype, fid = _ray_args(frame, shared, include_static)
+        dist = np.empty((max(n, 0), n_rays), dtype=np.float64)
+        gid = np.empty((max(n, 0), n_rays), dtype=np.int32) if want_geomid else None
+        _check(lib().mrs_batch_ray(self._h, p.ctypes.data, v.ctypes.data, n_rays, flags, ftype, fid, group_mask,
+                                   bodyexclude, dist.ctypes.data, gid.ctypes.data if want_geomid else None, env0, n))
+        return dist, gid
+
+    def ray_device(self, pnt_ptr: int, vec_ptr: int, n_rays: int, dist_ptr: int, geomid_ptr: int = 0, *,
+                   shared: bool = False, frame=("world", 0), group_mask: int = 0, include_static: bool = True,
+                   bodyexclude: int = -1) -> None:
+        """the same for every env from device fp32 rays [n_envs, n_rays, 3] (shared: [n_rays, 3]) into device
+        buffers dist fp32 and geomid int32 [n_envs, n_rays] (geomid_ptr 0: not wanted) -- torch tensors'
+        data_ptr(); one launch on the batch stream, no host synchronisation"""
+        flags, ftype, fid = _ray_args(frame, shared, include_static)
+        _check(lib().mrs_batch_ray_device(self._h, C.c_void_p(pnt_ptr) if pnt_ptr else None,
+                                          C.c_void_p(vec_ptr) if vec_ptr else None, n_rays, flags, ftype, fid,
+                                          group_mask, bodyexclude, C.c_void_p(dist_ptr) if dist_ptr else None,
+                                          C.c_void_p(geomid_ptr) if geomid_ptr else None))
 
     def contacts(self, env: int = 0, max_n: int = 256):
         """mjData.contact of `env` after the last step/forward: (geom [n, 2] int32, dist [n],
