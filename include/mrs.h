@@ -473,6 +473,15 @@ int mrs_debug_batch_layout(const mrs_batch* b, int* out, int n);
  * the plan chosen, nothing else.  Returns the number of values written, MRS_ERR_INVALID for a null or
  * bad argument, MRS_ERR_UNSUPPORTED for a model mrs_batch_create refuses with it. */
 int mrs_debug_plan_layout(const mrs_model* m, int n_envs, int cu_count, int max_contacts, int* out, int n);
+/* diagnostics: how mrs_batch_render_depth / mrs_batch_render_async would render n_frames frames of camera
+ * `cam` on a device with max_lds bytes of LDS per workgroup, without a device: the render switches
+ * (MRS_DEPTH_V1, MRS_DEPTH_V2, MRS_RAST_BUDGET_MB) are read and the plan chosen, nothing else.  Values: [0]
+ * the kernel (0: triangle binning, one workgroup per frame; 1: one workgroup per frame; 2: one workgroup
+ * per 16 x 16 pixel tile), [1] the frame kernel's mesh code is compiled in, [2] dynamic LDS bytes of the
+ * binning kernel's band, [3] frames per launch of the binning kernel, [4] bytes of one frame's triangle
+ * list, [5] and [6] the grid (of the first launch).  Returns the number of values written,
+ * MRS_ERR_INVALID for a null or bad argument, MRS_ERR_UNSUPPORTED for a model the render calls refuse. */
+int mrs_debug_render_plan(const mrs_model* m, int cam, int n_frames, int max_lds, long long* out, int n);
 /* diagnostics: the ids of the geoms a ray query with this group_mask, flags (MRS_RAY_NO_STATIC; MRS_RAY_SHARED
  * is accepted and ignored) and bodyexclude may hit, in geom order -- the list the batch uploads for the
  * query kernel.  Up to `max` ids are written to out (may be NULL when max == 0); returns the count, which

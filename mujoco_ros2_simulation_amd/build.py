@@ -17,7 +17,7 @@ OBJ = ROOT / "build" / "obj"
 LIB = PKG / "libmrs.so"
 ARCH = os.environ.get("MRS_OFFLOAD_ARCH", "gfx950")
 
-HIP_SOURCES = ["hip/step.hip", "hip/batch.hip"]
+HIP_SOURCES = ["hip/step.hip", "hip/batch.hip", "hip/render.hip"]
 # step.hip is compiled once per part, in parallel.  A part is the five properties of its row: the group
 # width G, the kernel set (step.hip kSel*: forward, step, the G = 16 primal-solver step, the G = 16 step
 # kernels with ray helper waves), MRS_EXT (the extended code: MPR contact polish, > 32 ray geoms), MRS_PRM

@@ -591,6 +591,17 @@ int mrs_debug_plan_layout(const mrs_model* m, int n_envs, int cu_count, int max_
   return rc == MRS_OK ? k : rc;
 }
 
+int mrs_debug_render_plan(const mrs_model* m, int cam, int n_frames, int max_lds, long long* out, int n) {
+  int k = 0;
+  const int rc = guarded([&] {
+    if (!m || !out || n < 0) throw std::invalid_argument("null model or output");
+    if (n_frames < 1) throw std::invalid_argument("n_frames must be positive");
+    if (max_lds < 0) throw std::invalid_argument("negative LDS limit");
+    k = mrs::render_plan(m->m, cam, n_frames, max_lds, out, n);
+  });
+  return rc == MRS_OK ? k : rc;
+}
+
 int mrs_debug_ray_filter(const mrs_model* m, unsigned group_mask, int flags, int bodyexclude, int* out, int max) {
   int k = 0;
   const int rc = guarded([&] {

@@ -59,6 +59,9 @@ void batch_launch(BatchImpl* b, int n_steps, bool forward_only);
 void batch_render_depth(BatchImpl* b, int cam, int env0, int n, float* out, bool device_out, unsigned char* rgb = nullptr);
 void batch_render_async(BatchImpl* b, int cam, int env0, int n, float* d_out, unsigned char* d_rgb);
 void batch_render_wait(BatchImpl* b);
+// the plan of n_frames frames of camera `cam` on a device with max_lds bytes of LDS per workgroup (no
+// device): kernel kind, kMesh, band LDS bytes, frame chunk, list bytes per frame, grid x and y (renderplan.h)
+int render_plan(const Model& m, int cam, int n_frames, int max_lds, long long* out, int n);
 // ray queries against the poses of the last step / forward (mrs.h MRS_RAY_*): device rays and outputs for
 // every env, asynchronous on the batch stream, and host fp64 rows for envs [env0, env0 + n), synchronised;
 // geomid may be null.  Every argument is checked before any launch

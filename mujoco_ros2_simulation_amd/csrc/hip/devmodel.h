@@ -157,7 +157,7 @@ struct DevModel {
   CPtr<int> body_tree, dof_tree, tree_dofadr, tree_dofnum, tree_Moff;  // tree -1: world / no dofs
   // geoms
   CPtr<int> geom_type, geom_bodyid, geom_group, geom_dataid;
-  // mesh frames by triangle binning (batch.hip depth_kernel_mesh): the visible mesh geoms and the
+  // mesh frames by triangle binning (render.hip depth_kernel_mesh): the visible mesh geoms and the
   // first (geom, triangle) pair of each; nrast = 0 when the model has none (or exceeds its limits)
   CPtr<int> rast_geom, rast_base;
   int nrast, nrast_pair;

@@ -19,6 +19,7 @@
 #include "../mjcf/model.h"
 #include "batch.h"
 #include "devmodel.h"
+#include "renderplan.h"
 #include "start_rows.h"
 
 namespace mrs {
@@ -26,8 +27,8 @@ namespace mrs {
 // ------------------------------------------------------------------ overrides
 // The environment switches of batch creation (tests and A/B runs; none is set in a measured run).
 // read_overrides() is the one place that reads them, once per batch: tests flip them between batches.
-// The render switches (MRS_DEPTH_V1, MRS_DEPTH_V2, MRS_RAST_BUDGET_MB) are read per render call in
-// batch.hip and are not part of a batch's tables or plan.
+// The render switches (MRS_DEPTH_V1, MRS_DEPTH_V2, MRS_RAST_BUDGET_MB) are read per render call by
+// renderplan.h's read_render_overrides() and are not part of a batch's tables or plan.
 struct Overrides {
   int group = 0;             // MRS_GROUP: lanes per env (8, 16, 32 or 64, when nv allows); 0: the plan's choice
   int g16_wpb = 0;           // MRS_G16_WPB: waves per workgroup of a 16-lane batch (1, 2 or 4); 0: the plan's
@@ -78,9 +79,9 @@ inline Overrides read_overrides() {
 }
 
 // ------------------------------------------------------------------ the packed blocks
-// restated limits of the render code (batch.hip asserts them against lit.h and the depth kernels)
+// restated limits of the render code (batch.hip asserts them against lit.h); the frame kernels' geom
+// limit kDepthGeoms is renderplan.h's own
 constexpr int kRlitHead = 12, kRlitLight = 24, kRlitMat = 12, kRlitTex = 16, kRlitMaxLights = 8;
-constexpr int kRastMaxGeoms = 64;
 
 template <class T>
 struct Slot {
@@ -696,7 +697,7 @@ inline void raster_lists(const Model& m, DevModel& d, std::vector<int>& rg, std:
     rb.push_back(static_cast<int>(np));
     np += fn;
   }
-  ok &= rg.size() <= 64 && np < (1ll << 30) && m.ngeom <= kRastMaxGeoms;
+  ok &= rg.size() <= 64 && np < (1ll << 30) && m.ngeom <= kDepthGeoms;
   if (!ok) { rg.clear(); rb.clear(); np = 0; }
   d.nrast = static_cast<int>(rg.size());
   d.nrast_pair = static_cast<int>(np);

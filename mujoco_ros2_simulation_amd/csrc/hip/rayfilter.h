@@ -2,7 +2,7 @@
 // A filter triple (group mask, static flag, excluded body) keeps a subset of the model's geoms with
 // mj_ray's meaning; the query kernel (rayquery.h) walks the compact list of the kept geoms, in geom
 // order, so a filtered geom costs nothing per ray.  No device code and no HIP type: capi.cc includes
-// this for the debug entry, batch.hip for the lists it uploads.
+// this for the debug entry, render.hip for the lists it uploads.
 #pragma once
 
 #include <cstring>

@@ -1,5 +1,5 @@
 // Ray vs mesh, shared by the step kernel's rangefinders (step.hip) and the depth / colour kernels
-// (batch.hip).  mj_rayMesh restated (oracle.c ray_mesh): the ray in the geom frame (origin lp,
+// (render.hip).  mj_rayMesh restated (oracle.c ray_mesh): the ray in the geom frame (origin lp,
 // direction lv) is first tested against the geom's bounding box (half extents s, slab test), then
 // against the triangles, both faces (Moller-Trumbore) -- the ones the mesh's bounding volume
 // hierarchy does not rule out.  `trirec` points at the mesh's first pre-gathered triangle record
@@ -76,7 +76,7 @@ __device__ __forceinline__ float ray_aabb(const float lo[3], const float hi[3], 
 // The nearest hit over the triangles is the same whichever triangles the bounding volumes let
 // through (each triangle's t is computed by ray_tri alike); only ties between triangles at equal t
 // may resolve to a different triangle (its normal shades the colour image).
-// bvh / nnode: the mesh's bounding volume hierarchy (batch.hip build_mesh_bvh): 8 floats per node in
+// bvh / nnode: the mesh's bounding volume hierarchy (devtables.h build_mesh_bvh): 8 floats per node in
 // depth-first order -- AABB lo, the index of the node after its subtree (int bits), AABB hi, and for a
 // leaf (first << 8 | count) of its triangles in `face` (int bits; -1 for an inner node).  Stackless
 // traversal per lane: a missed box, a box entered past the nearest hit, or a leaf jumps to the skip

@@ -1,5 +1,5 @@
 // Batched ray queries against the posed scene (mrs_batch_ray_device, include/mrs.h): mj_ray /
-// mj_multiRay for arbitrary rays of every env.  Included by batch.hip after ray_prim and MeshRef.
+// mj_multiRay for arbitrary rays of every env.  Included by render.hip after ray_prim and MeshRef.
 //
 // One workgroup of 256 threads handles one env and a tile of 256 consecutive rays; the grid is
 // (ray tiles, envs).  The workgroup stages the env's kept geoms (rayfilter.h: the compact list of the
@@ -114,8 +114,7 @@ __global__ __launch_bounds__(256) void ray_query_kernel(const RayQueryArgs a, co
         }
         float th;
         if (kMesh && pass == 1)
-          th = ray_mesh(mesh.tri + 9 * mesh.faceadr[t.dataid], mesh.facenum[t.dataid], t.size, lp, lv,
-                        mesh.bvh + 8 * mesh.bvhadr[t.dataid], mesh.bvhnum[t.dataid]);
+          th = mesh.ray(t.dataid, t.size, lp, lv);
         else
           th = ray_prim(t.type, t.size, lp, lv);
         if (th >= 0) th += t0;

@@ -302,6 +302,8 @@ def lib() -> C.CDLL:
         L.mrs_debug_phase_cycles.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.mrs_debug_batch_layout.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.mrs_debug_plan_layout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        if hasattr(L, "mrs_debug_render_plan"):  # (an A/B library named by MRS_LIB may predate it)
+            L.mrs_debug_render_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -455,6 +457,23 @@ def plan_layout(model: "Model", n_envs: int, cu_count: int, max_contacts: int = 
     if k < 0:
         raise MrsError(k, lib().mrs_last_error().decode())
     return dict(zip(LAYOUT_KEYS[:k], out[:k].tolist()))
+
+
+RENDER_KERNELS = ["binned", "frame", "tile"]  # depth_kernel_mesh, depth_kernel_v2, depth_kernel
+
+
+def render_plan(model: "Model", cam: int, n_frames: int, max_lds: int) -> dict:
+    """how n_frames frames of camera `cam` would be rendered on a device with max_lds bytes of LDS per
+    workgroup (mrs_debug_render_plan; the render switches are read at the call): the kernel, the frame
+    kernel's mesh flag, the binned kernel's band LDS bytes, frames per launch and list bytes per frame, and
+    the grid.  Needs no GPU"""
+    out = np.zeros(7, dtype=np.int64)
+    k = lib().mrs_debug_render_plan(model.handle, cam, n_frames, max_lds, out.ctypes.data, len(out))
+    if k < 0:
+        raise MrsError(k, lib().mrs_last_error().decode())
+    v = out.tolist()
+    return {"kernel": RENDER_KERNELS[v[0]], "mesh": bool(v[1]), "band_lds": v[2], "chunk": v[3], "per_frame": v[4],
+            "grid": (v[5], v[6])}
 
 
 def ray_filter(model: "Model", group_mask: int = 0, include_static: bool = True, bodyexclude: int = -1) -> np.ndarray:

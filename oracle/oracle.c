@@ -3535,7 +3535,7 @@ int orc_contacts(orc_data* d, int max, int* geom, double* dist, double* pos, dou
  * 0-2 (mjvOption default), hits nearer than znear*extent ignored, misses -> far = zfar*extent.
  * Row 0 is the top row (the plugin's vertical flip, :229-240, already applied). */
 /* colour of a hit: flat headlight shading rgba * (0.3 + 0.7 max(0, -n.d)) of the geom's surface
- * normal n at the hit and the unit pixel ray d (the device's batch.hip local_normal / shade).  Not a
+ * normal n at the hit and the unit pixel ray d (the device's render.hip local_normal / shade).  Not a
  * restatement of the reference's OpenGL render (src/mujoco_cameras.cpp:211-240): parity unpinned
  * against the reference, pinned between device and this oracle. */
 static void local_normal(int type, const double* s, const double p[3], double n[3]) {

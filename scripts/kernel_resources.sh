@@ -2,7 +2,7 @@
 # Register / scratch footprint of the step kernels in a built object (no GPU needed):
 #   scripts/kernel_resources.sh [build/obj/hip_step.hip.o]
 # KERNEL=<pattern> lists the kernels whose name matches it instead, with their LDS bytes as well, e.g.
-#   KERNEL=ray_query_kernel scripts/kernel_resources.sh build/obj/hip_batch.hip.o
+#   KERNEL=ray_query_kernel scripts/kernel_resources.sh build/obj/hip_render.hip.o
 set -e
 B=/opt/rocm/lib/llvm/bin
 objs=${@:-$(ls build/obj/hip_step.hip.part*.o | grep -v part0)}

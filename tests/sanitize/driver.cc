@@ -3,7 +3,8 @@
 // reference scene plus malformed inputs, and the fp64 oracle stepping each compiled model.  GPU code
 // cannot run under AddressSanitizer on this pool, so the host paths are checked here.  So are the
 // start rows and parameter rows a batch is created from (csrc/hip/start_rows.h), against the model, and the
-// device tables and launch plan of every model (csrc/hip/devtables.h, plan.h), against their ranges.
+// device tables, launch plan and frame plans of every model (csrc/hip/devtables.h, plan.h, renderplan.h),
+// against their ranges.
 #include <algorithm>
 #include <cstddef>
 #include <cstdio>
@@ -239,10 +240,36 @@ void check_plan(const mrs::Model& m, const mrs::Plan& p) {
   need(!d.rf_sweep || (d.rf_sw_n == d.nrf && d.rf_mode == 2 && d.rf_common), "ray sweep");
 }
 
+// the frame plan (csrc/hip/renderplan.h) of every camera: the chunk and the list bytes the frame launch
+// allocates by, the LDS it asks for and the grids, for the frame counts and LDS limits the plan distinguishes
+void check_render_plans(const mrs::Model& m, const mrs::DevModel& d) {
+  const bool has_mesh = std::any_of(m.geom_type.begin(), m.geom_type.end(), [](int t) { return t == MRS_GEOM_MESH; });
+  mrs::RenderOverrides small = mrs::read_render_overrides();
+  small.budget_mb = 1;
+  for (const mrs::RenderOverrides& o : {mrs::read_render_overrides(), small})
+    for (int cam = 0; cam < m.ncam; ++cam)
+      for (int n : {1, 8192})
+        for (int max_lds : {0, 65536, 163840}) {
+          const int W = m.cam_resolution[2 * cam], H = m.cam_resolution[2 * cam + 1];
+          const mrs::RenderPlan p = mrs::choose_render(m.ngeom, has_mesh, d.nrast, d.nrast_pair, W, H, n, max_lds, o);
+          const size_t budget = static_cast<size_t>(o.budget_mb) << 20;
+          need(p.chunk >= 1 && p.chunk <= n, "render plan: chunk outside [1, n_frames]");
+          need(p.per_frame >= sizeof(unsigned long long) && p.per_frame <= static_cast<size_t>(-1) / p.chunk,
+               "render plan: chunk * per_frame overflows");
+          need(p.chunk == 1 || static_cast<size_t>(p.chunk) * p.per_frame <= budget, "render plan: lists over the budget");
+          need(p.kind != mrs::RenderPlan::BINNED || (p.band_lds <= static_cast<size_t>(max_lds) && d.nrast > 0),
+               "render plan: the binned kernel's band does not fit the LDS limit");
+          need(p.kind != mrs::RenderPlan::FRAME || m.ngeom <= mrs::kDepthGeoms, "render plan: frame kernel over its geoms");
+          need(m.ngeom <= mrs::kMaxRenderGeoms, "render plan: more geoms than any kernel stages");
+          need(p.grid_x >= 1 && p.grid_y >= 1, "render plan: empty grid");
+        }
+}
+
 void check_device_tables(const mrs::Model& m) {
   const mrs::Overrides o = mrs::read_overrides();
   const mrs::DevTables T = mrs::build_tables(m, 0, o);
   check_tables(m, T);
+  check_render_plans(m, T.dm);
   // every LDS layout a plan can ask for: dense and blocked, with and without the integrator factor's slot
   for (bool blocked : {false, true})
     for (bool want_lh : {false, true}) check_lds(m, T.dm, mrs::lds_layout(m, T.dm, blocked, want_lh), blocked, want_lh);

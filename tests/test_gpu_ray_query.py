@@ -22,7 +22,7 @@ MOBILE = ROOT / "scenes" / "mobile_base.xml"
 ARM7_MESH = ROOT / "scenes" / "arm7_mesh.xml"
 TILE = 256  # rays per workgroup (rayquery.h)
 MAX_CHUNK = int(re.search(r"constexpr int kMaxRenderGeoms = (\d+);",
-                          (ROOT / "mujoco_ros2_simulation_amd" / "csrc" / "hip" / "batch.hip").read_text()).group(1))
+                          (ROOT / "mujoco_ros2_simulation_amd" / "csrc" / "hip" / "renderplan.h").read_text()).group(1))
 
 
 def _oracles(model, q):
