@@ -86,6 +86,6 @@ void batch_get_dyn(BatchImpl* b, int which, double* host, int env0, int n);
 void batch_get_field_device(BatchImpl* b, int field, float* d_out, int env0, int n);
 void batch_sync(BatchImpl* b);
 double batch_last_kernel_ms(BatchImpl* b, int kind);
-int phase_cycles(double* out, int n, bool reset);  // step.hip; profiling builds only
+int phase_cycles(double* out, int n, bool reset);  // step_dispatch.hip; step.hip in profiling builds
 
 }  // namespace mrs

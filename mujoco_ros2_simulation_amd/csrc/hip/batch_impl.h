@@ -84,7 +84,7 @@ struct BatchImpl {
   // ray queries (batch_ray): the uploaded geom lists of the filter triples seen so far, oldest first
   struct RayList { unsigned group_mask; bool no_static; int bodyexclude; RayGeom* d; int count; bool mesh; };
   std::deque<RayList> ray_lists;
-  // the model needs the extended step kernels (step.hip MRS_EXT): general convex (MPR) collision
+  // the model needs the extended step kernels (step/base.h MRS_EXT): general convex (MPR) collision
   // pairs, or rangefinders with more than 32 ray geoms
   bool ext = false;
 };

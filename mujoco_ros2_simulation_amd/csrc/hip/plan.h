@@ -110,7 +110,7 @@ struct Plan {
   int g16_one_wg = 0;  // G = 16 with one workgroup per CU (tables past the two-per-CU budget)
   int wpb16 = WavesPerBlock<16>::value;  // waves per workgroup of the G = 16 kernels (DevState::wpb16)
   int helpers = 0;     // helper waves (DevState::ray_helpers)
-  bool ext = false;    // the extended step kernels (step.hip MRS_EXT)
+  bool ext = false;    // the extended step kernels (step/base.h MRS_EXT)
   bool want_lh = false;  // L has the integrator factor's slot (L.Lh)
   // the tables' DevModel with the plan's fields filled in: L, S, shr_*, blocked, fuse_ih, rf_common,
   // rf_mode, rf_sweep and the sweep's fan rf_sw* (all zero without it); the pointers still null
@@ -251,7 +251,7 @@ inline Plan choose_plan(const Model& m, const DevTables& T, int n_envs, int cu_c
     if (o.g16_wpb == 1 || o.g16_wpb == 2 || o.g16_wpb == 4)
       p.wpb16 = std::min(o.g16_wpb, static_cast<int>(WavesPerBlock<16>::value));
   }
-  // extended step kernels (step.hip MRS_EXT) for models with general convex (MPR) pairs -- a pair
+  // extended step kernels (step/base.h MRS_EXT) for models with general convex (MPR) pairs -- a pair
   // that is not plane-* and has an ellipsoid, cylinder or mesh (narrowphase's analytic routines cover
   // the rest) -- or rangefinders over more than 32 ray geoms
   p.ext = d.nrgeom > 32 && d.nrf > 0;

@@ -13,7 +13,8 @@ ROOT = Path(__file__).resolve().parents[1]
 
 
 def _disasm():
-    # blocked mode (the sparse PGS) and the 16-lane kernels (the dense register PGS)
+    # blocked mode (the sparse PGS) and the 16-lane kernels (the dense register PGS); part0 is no longer
+    # built -- the filter keeps a stale one of an old build/obj, which holds no device code, out
     objs = sorted(o for o in (ROOT / "build" / "obj").glob("hip_step.hip.part*.o") if o.name != "hip_step.hip.part0.o")
     if not objs:
         pytest.skip("no step.hip objects in build/obj (library built elsewhere)")
