@@ -38,6 +38,8 @@ enum { MRS_BUILTIN_NONE = 0, MRS_BUILTIN_GRADIENT = 1, MRS_BUILTIN_CHECKER = 2, 
 enum { MRS_MARK_NONE = 0, MRS_MARK_EDGE = 1, MRS_MARK_CROSS = 2 };
 #define MRS_NEQDATA 11
 enum { MRS_TRN_JOINT = 0, MRS_TRN_TENDON = 3 };
+enum { MRS_WRAP_NONE = 0, MRS_WRAP_JOINT = 1, MRS_WRAP_PULLEY = 2, MRS_WRAP_SITE = 3 };  /* mjtWrap subset */
+enum { MRS_TENDON_FIXED = 0, MRS_TENDON_SPATIAL = 1 };  /* tendon_kind (this project's own) */
 enum { MRS_DYN_NONE = 0, MRS_DYN_INTEGRATOR = 1, MRS_DYN_FILTER = 2, MRS_DYN_FILTEREXACT = 3 };
 enum { MRS_GAIN_FIXED = 0, MRS_GAIN_AFFINE = 1 };
 enum { MRS_BIAS_NONE = 0, MRS_BIAS_AFFINE = 1 };
@@ -49,7 +51,8 @@ enum { MRS_SENS_ACCELEROMETER = 1, MRS_SENS_GYRO = 3, MRS_SENS_FORCE = 4, MRS_SE
        /* [upstream; verify] mjtSensor of MuJoCo 3.3.4 */
        MRS_SENS_TOUCH = 0, MRS_SENS_VELOCIMETER = 2, MRS_SENS_FRAMEXAXIS = 27, MRS_SENS_FRAMEYAXIS = 28,
        MRS_SENS_FRAMEZAXIS = 29, MRS_SENS_FRAMELINVEL = 30, MRS_SENS_FRAMEANGVEL = 31,
-       MRS_SENS_FRAMELINACC = 32, MRS_SENS_SUBTREECOM = 34, MRS_SENS_SUBTREELINVEL = 35 };
+       MRS_SENS_FRAMELINACC = 32, MRS_SENS_SUBTREECOM = 34, MRS_SENS_SUBTREELINVEL = 35,
+       MRS_SENS_TENDONPOS = 11, MRS_SENS_TENDONVEL = 12 };
 /* restate bits (not MuJoCo options; mrs_model_set_restate): opt-in variants of this restatement that
  * upstream does not have.  NEWTON_REFINE: after a Newton step that kept every row's state, one more
  * step from freshly formed residuals with the same factor, then stop (mj_solNewton instead keeps
@@ -179,12 +182,20 @@ typedef struct mrs_model_view {
       *tex_rgb2 /*3*/, *tex_markrgb /*3*/, *mat_rgba /*4*/, *mat_texrepeat /*2*/, *mat_specular,
       *mat_shininess, *mat_emission;
 
-  /* fixed tendons (mjModel ntendon / tendon_* / wrap_*, mjTRN_TENDON actuators): tendon t is the linear
-   * combination length = sum_k wrap_prm[k] qpos[jnt_qposadr[wrap_objid[k]]] over its wraps
-   * k in [tendon_adr[t], tendon_adr[t] + tendon_num[t]) of hinge / slide joints; ten_J is constant.
-   * Spring force -stiffness (length - lengthspring) outside the dead band [lengthspring[0],
+  /* tendons (mjModel ntendon / tendon_* / wrap_*, mjTRN_TENDON actuators).  Tendon t owns the wraps
+   * k in [tendon_adr[t], tendon_adr[t] + tendon_num[t]); wrap_type / tendon_kind are at the end of the
+   * struct.  A fixed tendon (MRS_TENDON_FIXED; wraps MRS_WRAP_JOINT, wrap_objid a hinge / slide joint,
+   * wrap_prm its coefficient) is the linear combination length = sum_k wrap_prm[k]
+   * qpos[jnt_qposadr[wrap_objid[k]]]; its Jacobian is constant.  A spatial tendon (MRS_TENDON_SPATIAL) is
+   * a path through sites (MRS_WRAP_SITE, wrap_objid the site) cut into branches by pulleys
+   * (MRS_WRAP_PULLEY, wrap_objid -1, wrap_prm the divisor): consecutive sites of one branch form a
+   * segment, a segment of a branch behind a pulley of divisor d counts with weight 1 / d (1 before the
+   * first pulley), length = sum_seg w |p1 - p0| and J = sum_seg w dir' (jacp(site1) - jacp(site0)),
+   * both functions of the pose.  For either kind: velocity J qvel,
+   * spring force -stiffness (length - lengthspring) outside the dead band [lengthspring[0],
    * lengthspring[1]], damping -damping * velocity, limit rows on [range[0], range[1]] within margin,
-   * a friction-loss row when frictionloss > 0; diagApprox tendon_invweight0 = J M(qpos0)^-1 J'. */
+   * a friction-loss row when frictionloss > 0; diagApprox tendon_invweight0 = J M(qpos0)^-1 J' and
+   * tendon_length0 are taken at qpos0. */
   int ntendon, nwrap;
   const int *tendon_adr, *tendon_num, *tendon_limited, *wrap_objid;
   const double *wrap_prm, *tendon_range /*2*/, *tendon_margin, *tendon_solref_lim /*2*/,
@@ -221,6 +232,10 @@ typedef struct mrs_model_view {
   int nmocap;
   const int *body_mocapid;
   const double *key_mpos, *key_mquat;
+
+  /* tendon paths (see the tendon block above): wrap_type [nwrap] MRS_WRAP_*, tendon_kind [ntendon]
+   * MRS_TENDON_*.  Kept last: the members above keep their offsets */
+  const int *wrap_type, *tendon_kind;
 } mrs_model_view;
 
 #ifdef __cplusplus

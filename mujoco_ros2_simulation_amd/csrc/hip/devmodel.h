@@ -52,7 +52,7 @@ struct LdsLayout {
       dofb,    // blocked mode: per dof its body and that body's subtree end (int bits; jac_col)
       H,       // blocked mode with a primal solver (Newton/CG): dense nv x nv Hessian and its factor
       Li,      // blocked mode with PGS: L^-1 per tree block (same offsets as L): the records' Y = L^-1 J'
-      ten,     // fixed tendons: length and velocity per tendon of the step (smooth_forces)
+      ten,     // tendons: length and velocity per tendon of the step (smooth_forces, spatial_tendons)
       rk,      // RK4 models: the step's initial qpos [nq], then qvel [nv], stage velocity, B-weighted sums of
                // the stage velocities and accelerations [nv each]
       niter,   // constraint solver iterations of the last forward (int bits)
@@ -184,7 +184,8 @@ struct DevModel {
   // active equality constraints (mrs_model_view eq_*, inactive ones dropped on the host): neq of
   // them giving neq_rows rows (connect 3, weld 6, joint 1), first in the row order
   int neq, neq_rows;
-  // fixed tendons (devtables.h tendon_tables): wraps, dense Jacobian rows ten_J [ntendon][nv], 12 constants per tendon
+  // tendons (devtables.h tendon_tables): the fixed ones' wraps and constant Jacobian rows in ten_J [ntendon][nv]
+  // (a spatial tendon has no wraps here and a zero row: see nten_spatial at the end), 12 constants per tendon
   // (stiffness, damping, lengthspring[2], range[2], margin, frictionloss, invweight0), the tendons
   // with friction-loss rows / limits, each actuator's tendon (-1: joint transmission); xrows: row
   // sources the blocked-mode sparse solver does not take (neq + nten_fric + nten_lim)
@@ -297,6 +298,18 @@ struct DevModel {
   // ninth column of its substitution (step.hip chol_solve_rows16, pgs_small16_qacc); 0
   // (MRS_NO_SOLVE_FUSE=1, A/B): separate solves.  Kept last: the fields above keep their offsets
   int solve_fuse;
+  // spatial tendons (devtables.h tendon_tables): their count -- 0 for every model
+  // without one, whose launches then take none of their code.  Spatial tendon k is tendon tsp_ten[k] and
+  // owns the segments [tsp_adr[k], tsp_adr[k] + tsp_num[k]) of tsp_seg, 12 floats each: the two sites'
+  // bodies (int bits), their positions in those bodies' frames [3 + 3], the weight 1 / divisor, pad;
+  // ten_sp [ntendon] is the tendon's index among the spatial ones (-1: fixed, its row is ten_J's).  Length,
+  // velocity and the Jacobian row are recomputed per env in every forward pass (step.hip spatial_tendons)
+  // into L.ten and the env's Jacobian slot: lds_tenJ is that slot's offset in the env's LDS (floats),
+  // [nten_spatial][nv], the last extent of the layout and inside L.total (plan.h lds_layout; 0 when
+  // nten_spatial == 0, and then no extent is taken).  Kept last: the fields above keep their offsets
+  int nten_spatial, lds_tenJ;
+  CPtr<int> tsp_ten, tsp_adr, tsp_num, ten_sp;
+  CPtr<float> tsp_seg;
 };
 constexpr int kRayBlock = 128;
 // bits of DevModel::prm_mask (1 << MRS_PARAM_*)

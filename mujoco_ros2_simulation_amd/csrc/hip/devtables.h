@@ -506,24 +506,51 @@ inline EqTables equality_tables(const Model& m, DevModel& d) {
   return e;
 }
 
-// fixed tendons: wraps (qpos / dof address, coefficient), the constant Jacobian rows (dense
-// ntendon x nv), per tendon 12 constants (stiffness, damping, lengthspring[2], range[2], margin,
-// frictionloss, invweight0), and the tendons that give friction-loss / limit rows
+// tendons.  Fixed: wraps (qpos / dof address, coefficient) and the constant Jacobian rows (dense
+// ntendon x nv).  Spatial (DevModel::nten_spatial): no wraps and a zero row here; per tendon its id and
+// its segments -- consecutive sites of one branch -- as 12-float records: the sites' bodies (int bits),
+// their local positions, the weight 1 / divisor of the branch's pulley.  Both: per tendon 12 constants
+// (stiffness, damping, lengthspring[2], range[2], margin, frictionloss, invweight0), and the tendons
+// that give friction-loss / limit rows
 struct TendonTables {
-  std::vector<int> wrap_qadr, wrap_dof, fric, lim;
-  std::vector<double> J, prm;
+  std::vector<int> adr, num, wrap_qadr, wrap_dof, fric, lim, sp_ten, sp_adr, sp_num, sp_of;
+  std::vector<double> coef, J, prm;
+  std::vector<float> sp_seg;
 };
 inline TendonTables tendon_tables(const Model& m, DevModel& d) {
   TendonTables t;
   const int ntendon = static_cast<int>(m.tendon_adr.size());
   t.J.assign(static_cast<size_t>(ntendon) * m.nv, 0.0);
-  for (size_t k = 0; k < m.wrap_objid.size(); ++k) {
-    t.wrap_qadr.push_back(m.jnt_qposadr[m.wrap_objid[k]]);
-    t.wrap_dof.push_back(m.jnt_dofadr[m.wrap_objid[k]]);
-  }
+  t.sp_of.assign(ntendon, -1);
   for (int n = 0; n < ntendon; ++n) {
-    for (int k = m.tendon_adr[n]; k < m.tendon_adr[n] + m.tendon_num[n]; ++k)
-      t.J[static_cast<size_t>(n) * m.nv + t.wrap_dof[k]] += m.wrap_prm[k];
+    const int a0 = m.tendon_adr[n], a1 = a0 + m.tendon_num[n];
+    t.adr.push_back(static_cast<int>(t.coef.size()));
+    if (m.tendon_kind[n] == MRS_TENDON_SPATIAL) {
+      t.num.push_back(0);
+      t.sp_of[n] = static_cast<int>(t.sp_ten.size());
+      t.sp_ten.push_back(n);
+      t.sp_adr.push_back(static_cast<int>(t.sp_seg.size() / 12));
+      double w = 1;
+      for (int k = a0; k < a1; ++k) {
+        if (m.wrap_type[k] == MRS_WRAP_PULLEY) { w = 1 / m.wrap_prm[k]; continue; }
+        if (k + 1 >= a1 || m.wrap_type[k + 1] != MRS_WRAP_SITE) continue;
+        const int s0 = m.wrap_objid[k], s1 = m.wrap_objid[k + 1];
+        t.sp_seg.insert(t.sp_seg.end(), {int_bits(m.site_bodyid[s0]), int_bits(m.site_bodyid[s1]),
+                                         static_cast<float>(m.site_pos[3 * s0]), static_cast<float>(m.site_pos[3 * s0 + 1]),
+                                         static_cast<float>(m.site_pos[3 * s0 + 2]), static_cast<float>(m.site_pos[3 * s1]),
+                                         static_cast<float>(m.site_pos[3 * s1 + 1]), static_cast<float>(m.site_pos[3 * s1 + 2]),
+                                         static_cast<float>(w), 0.0f, 0.0f, 0.0f});
+      }
+      t.sp_num.push_back(static_cast<int>(t.sp_seg.size() / 12) - t.sp_adr.back());
+    } else {
+      t.num.push_back(a1 - a0);
+      for (int k = a0; k < a1; ++k) {
+        t.wrap_qadr.push_back(m.jnt_qposadr[m.wrap_objid[k]]);
+        t.wrap_dof.push_back(m.jnt_dofadr[m.wrap_objid[k]]);
+        t.coef.push_back(m.wrap_prm[k]);
+        t.J[static_cast<size_t>(n) * m.nv + t.wrap_dof.back()] += m.wrap_prm[k];
+      }
+    }
     const double pr[12] = {m.tendon_stiffness[n], m.tendon_damping[n], m.tendon_lengthspring[2 * n],
                            m.tendon_lengthspring[2 * n + 1], m.tendon_range[2 * n], m.tendon_range[2 * n + 1],
                            m.tendon_margin[n], m.tendon_frictionloss[n], m.tendon_invweight0[n], 0, 0, 0};
@@ -535,6 +562,7 @@ inline TendonTables tendon_tables(const Model& m, DevModel& d) {
   d.ntendon = ntendon;
   d.nten_fric = static_cast<int>(t.fric.size());
   d.nten_lim = static_cast<int>(t.lim.size());
+  d.nten_spatial = static_cast<int>(t.sp_ten.size());
   return t;
 }
 
@@ -593,7 +621,7 @@ inline KinTrees kinematic_trees(const Model& m, const PairTables& pairs, DevMode
 // (step.hip sensors_more, entered only by models that have one), the others (step.hip sensors)
 inline bool is_sensor_more(int t) {
   return t == MRS_SENS_TOUCH || t == MRS_SENS_VELOCIMETER || t == MRS_SENS_SUBTREECOM || t == MRS_SENS_SUBTREELINVEL ||
-         (t >= MRS_SENS_FRAMEXAXIS && t <= MRS_SENS_FRAMELINACC);
+         (t >= MRS_SENS_FRAMEXAXIS && t <= MRS_SENS_FRAMELINACC) || t == MRS_SENS_TENDONPOS || t == MRS_SENS_TENDONVEL;
 }
 
 // the row sources: friction-loss dofs, limited joints, the sensors by path, and the contact / row
@@ -806,6 +834,7 @@ inline SmoothRecords smooth_force_records(const Model& m, const ActTables& act, 
     for (int a = 0; a < m.nu; ++a) {
       if (act.dof[a] == j) { ai = ai == -1 ? a : -2; gear = act.gear[a]; }
       if (act.ten[a] >= 0 && ten.J[static_cast<size_t>(act.ten[a]) * m.nv + j] != 0) ai = -2;  // the loop
+      if (act.ten[a] >= 0 && ten.sp_of[act.ten[a]] >= 0) ai = -2;  // (a spatial tendon can move any dof)
     }
     const int jid = m.dof_jntid[j], b = m.dof_bodyid[j];
     int gc = 0;
@@ -926,6 +955,8 @@ inline std::vector<float> sensor_records(const Model& m, const RowLists& rows, c
       a = m.geom_bodyid[id];
       for (int i = 0; i < 3; ++i) lp[i] = m.geom_pos[3 * id + i];
       for (int i = 0; i < 4; ++i) lq[i] = m.geom_quat[4 * id + i];
+    } else if (ot == MRS_OBJ_TENDON) {
+      a = 0;  // (no body: tendonpos / tendonvel read the step's tendon slot by the tendon id, word 14)
     }
     sensrec.insert(sensrec.end(), {int_bits(t), int_bits(ot), int_bits(m.sensor_adr[sid]), int_bits(m.sensor_dim[sid]),
                                    static_cast<float>(m.sensor_cutoff[sid]), int_bits(a), int_bits(m.body_rootid[a]),
@@ -1136,8 +1167,8 @@ inline DevTables build_tables(const Model& m, int max_con_req, const Overrides& 
   for (int g = 0; g < m.ngeom && g < static_cast<int>(m.geom_matid.size()); ++g) matid[g] = m.geom_matid[g];
   T.addi(&D::geom_matid, matid);
   T.addi(&D::pair_g1, pairs.g1); T.addi(&D::pair_g2, pairs.g2); T.addi(&D::pair_dim, pairs.dim);
-  T.addi(&D::ten_adr, m.tendon_adr); T.addi(&D::ten_num, m.tendon_num); T.addi(&D::wrap_qadr, ten.wrap_qadr);
-  T.addi(&D::wrap_dof, ten.wrap_dof); T.addf(&D::wrap_coef, m.wrap_prm); T.addf(&D::ten_J, ten.J);
+  T.addi(&D::ten_adr, ten.adr); T.addi(&D::ten_num, ten.num); T.addi(&D::wrap_qadr, ten.wrap_qadr);
+  T.addi(&D::wrap_dof, ten.wrap_dof); T.addf(&D::wrap_coef, ten.coef); T.addf(&D::ten_J, ten.J);
   T.addf(&D::ten_prm, ten.prm); T.addi(&D::ten_fric, ten.fric); T.addi(&D::ten_lim, ten.lim);
   T.addf(&D::ten_solref_lim, m.tendon_solref_lim); T.addf(&D::ten_solimp_lim, m.tendon_solimp_lim);
   T.addf(&D::ten_solref_fri, m.tendon_solref_fri); T.addf(&D::ten_solimp_fri, m.tendon_solimp_fri);
@@ -1185,6 +1216,11 @@ inline DevTables build_tables(const Model& m, int max_con_req, const Overrides& 
   T.addf(&D::rgeom, ray_geom_records(m, d));
   T.addf(&D::rfblk, ray_block_records(m, T.rf, d));
   T.addf(&D::rfray, ray_records(m, T.rf, d));
+  // spatial tendons, after every table a model without one has (their offsets stay what they were)
+  if (d.nten_spatial > 0) {
+    T.addi(&D::tsp_ten, ten.sp_ten); T.addi(&D::tsp_adr, ten.sp_adr); T.addi(&D::tsp_num, ten.sp_num);
+    T.addi(&D::ten_sp, ten.sp_of); T.addf(&D::tsp_seg, ten.sp_seg);
+  }
   return T;
 }
 

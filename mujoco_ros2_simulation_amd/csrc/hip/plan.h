@@ -48,8 +48,16 @@ inline LdsLayout lds_layout(const Model& m, const DevModel& d, bool blocked, boo
   L.rk = m.integrator == MRS_INT_RK4 ? take(std::max(1, m.nq) + 4 * nv) : 0;
   L.act = m.na > 0 ? take(4 * m.na) : 0;
   L.mocap = m.nmocap > 0 ? take(7 * m.nmocap) : 0;
+  // the spatial tendons' Jacobian rows of the step, the layout's last extent (DevModel::lds_tenJ, lds_tenj())
+  if (d.nten_spatial > 0) take(d.nten_spatial * nv);
   L.total = off;
   return L;
+}
+
+// offset of the spatial tendons' Jacobian slot [nten_spatial][nv] in the layout L of lds_layout (its last
+// extent); 0 without spatial tendons
+inline int lds_tenj(const Model& m, const DevModel& d, const LdsLayout& L) {
+  return d.nten_spatial > 0 ? L.total - ((d.nten_spatial * std::max(1, m.nv) + 3) & ~3) : 0;
 }
 
 // workgroup-shared tables (DevModel::shr_*, offsets in floats from shr_off): ray-geom records, the
@@ -301,6 +309,7 @@ inline Plan choose_plan(const Model& m, const DevTables& T, int n_envs, int cu_c
   d.blocked = p.group == 64 ? 1 : 0;
   if (d.blocked) d.shr_total = d.shr_act;
   d.L = lds_layout(m, d, d.blocked != 0, p.want_lh);
+  d.lds_tenJ = lds_tenj(m, d, d.L);
   d.shr_off = d.L.total * envs_per_block(p.group, p.wpb16);
   if ((static_cast<size_t>(d.shr_off) + d.shr_total) * sizeof(float) > 160 * 1024)
     throw UnsupportedError("model too large for the per-environment LDS working set");

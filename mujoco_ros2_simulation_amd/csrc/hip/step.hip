@@ -2531,6 +2531,65 @@ __device__ void rk4_act(ENV_PARAMS, int stage) {
   wsync();
 }
 
+// ---- spatial tendons (mj_tendon for site / pulley paths).  The phase is out of line
+// and reached only behind the scalar test m.nten_spatial > 0 inside the tendon block of smooth_forces,
+// so a model without one takes none of it.
+
+// tendon t's Jacobian entry for dof j: the model's constant row for a fixed tendon, the env's row of
+// this forward pass (DevModel::lds_tenJ, spatial_tendons) for a spatial one
+__device__ __forceinline__ float ten_jac(const DevModel& m, const lfloat* s, int t, int j) {
+  if (m.nten_spatial > 0) {
+    const int k = m.ten_sp[t];
+    if (k >= 0) return s[m.lds_tenJ + k * m.nv + j];
+  }
+  return m.ten_J[t * m.nv + j];
+}
+// length, velocity and Jacobian row of every spatial tendon at the env's pose: per tendon, every lane
+// walks its segments (records of 12 floats, DevModel::tsp_seg) -- the two sites' world positions from the
+// bodies' poses, length += w |p1 - p0| -- and lane j adds w dir . (jac_col(site1) - jac_col(site0)) for
+// its dof (a segment within one body moves with it: no term); the velocity is the group sum of
+// J_j qvel_j.  Needs kinematics and com_pos (jac_col reads cdof and the subtree coms); writes L.ten
+// [2 t], [2 t + 1] and row k of the slot at lds_tenJ
+template <int G>
+__device__ __attribute__((noinline)) void spatial_tendons(ENV_PARAMS) {
+  ENV_UNPACK;
+  const int nv = m.nv;
+  #pragma unroll 1
+  for (int k = 0; k < m.nten_spatial; ++k) {
+    const int t = m.tsp_ten[k], q0 = m.tsp_adr[k], q1 = q0 + m.tsp_num[k];
+    float len = 0, jj = 0;
+    #pragma unroll 1
+    for (int q = q0; q < q1; ++q) {
+      const CPtr<float> r = m.tsp_seg + 12 * q;
+      const int b0 = __float_as_int(r[0]), b1 = __float_as_int(r[1]);
+      const float l0[3] = {r[2], r[3], r[4]}, l1[3] = {r[5], r[6], r[7]}, w = r[8];
+      float m0[9], m1[9], p0[3], p1[3], d[3];
+      for (int i = 0; i < 9; ++i) { m0[i] = s[L.xmat + 9 * b0 + i]; m1[i] = s[L.xmat + 9 * b1 + i]; }
+      mat_vec(p0, m0, l0);
+      mat_vec(p1, m1, l1);
+      for (int i = 0; i < 3; ++i) {
+        p0[i] += s[L.xpos + 3 * b0 + i];
+        p1[i] += s[L.xpos + 3 * b1 + i];
+        d[i] = p1[i] - p0[i];
+      }
+      const float n = sqrtf(dot3(d, d));
+      len += w * n;
+      if (b0 == b1 || lane >= nv) continue;
+      // (mju_normalize3: a null vector becomes the x axis)
+      if (n < kMinVal) { d[0] = 1; d[1] = 0; d[2] = 0; }
+      else { const float inv = 1.0f / n; d[0] *= inv; d[1] *= inv; d[2] *= inv; }
+      float c0[3], c1[3];
+      jac_col(m, s, b0, p0, lane, c0);
+      jac_col(m, s, b1, p1, lane, c1);
+      jj += w * (d[0] * (c1[0] - c0[0]) + d[1] * (c1[1] - c0[1]) + d[2] * (c1[2] - c0[2]));
+    }
+    const float vel = gsum<G>(lane < nv ? jj * s[L.qvel + lane] : 0.0f);
+    if (lane < nv) s[m.lds_tenJ + k * nv + lane] = jj;
+    if (lane == 0) { s[L.ten + 2 * t] = len; s[L.ten + 2 * t + 1] = vel; }
+  }
+  wsync();
+}
+
 // mj_passive + mj_fwdActuation + qfrc_smooth + qacc_smooth (lane per dof).  defer (forward(): 16-lane
 // PGS kernels with DevModel::solve_fuse): qacc_smooth is left to constraints(), which solves it with its
 // friction-loss rows or, on the dense path, by the same call as here; the lane's qfrc_smooth is returned
@@ -2538,7 +2597,7 @@ template <int G>
 __device__ MRS_PHASE float smooth_forces(ENV_PARAMS, bool defer = false) {
   ENV_UNPACK;
   const int nv = m.nv;
-  // fixed tendons (mj_tendon): length and velocity of each into the step's tendon slot (lane per tendon)
+  // tendons (mj_tendon): length and velocity of each into the step's tendon slot (fixed: lane per tendon)
   if (m.ntendon > 0) {
     #pragma unroll 1
     for (int t = lane; t < m.ntendon; t += G) {
@@ -2552,6 +2611,8 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS, bool defer = false) {
       s[L.ten + 2 * t + 1] = vel;
     }
     wsync();
+    // spatial tendons (no wraps above: zeros so far): their length, velocity and Jacobian row at this pose
+    if (m.nten_spatial > 0) { [[clang::noinline]] spatial_tendons<G>(ENV_ARGS); }
   }
   // actuator forces (lane per actuator)
   #pragma unroll 1
@@ -2604,7 +2665,7 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS, bool defer = false) {
       for (int a = 0; a < m.nu; ++a) {
         if (m.act_dof[a] == j) qa += m.act_gear[a] * s[L.act_force + a];
         else if (m.ntendon > 0 && m.act_ten[a] >= 0)
-          qa += m.act_gear[a] * s[L.act_force + a] * m.ten_J[m.act_ten[a] * nv + j];  // moment gear * J
+          qa += m.act_gear[a] * s[L.act_force + a] * ten_jac(m, s, m.act_ten[a], j);  // moment gear * J
       }
     }
     if (__float_as_int(dr[2])) qa = clampf(qa, dr[3], dr[4]);
@@ -2620,7 +2681,7 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS, bool defer = false) {
       // tendon springs (dead band [lengthspring0, lengthspring1]) and dampers through J'
       #pragma unroll 1
       for (int t = 0; t < m.ntendon; ++t) {
-        const float jt = m.ten_J[t * nv + j];
+        const float jt = ten_jac(m, s, t, j);
         if (jt == 0) continue;
         const CPtr<float> tp = m.ten_prm + 12 * t;
         const float len = s[L.ten + 2 * t], k = tp[0];
@@ -5864,7 +5925,7 @@ __device__ int dense_rows(ENV_PARAMS, int ncon) {
     #pragma unroll 1
     for (int k = 0; k < m.nten_fric; ++k) {
       const int t = m.ten_fric[k], r = nefc + k;
-      if (lane < nv) J[r * nv + lane] = m.ten_J[t * nv + lane];
+      if (lane < nv) J[r * nv + lane] = ten_jac(m, s, t, lane);
       if (lane == 0) {
         type[r] = __int_as_float(EFC_TFRICTION * 65536 + t);
         pos[r] = 0; marg[r] = 0; floss[r] = m.ten_prm[12 * t + 7];
@@ -5927,7 +5988,7 @@ __device__ int dense_rows(ENV_PARAMS, int ncon) {
       const float dist[2] = {len - tp[4], tp[5] - len};
       for (int sd = 0; sd < 2; ++sd) {
         if (!(dist[sd] < mg)) continue;
-        if (lane < nv) J[nefc * nv + lane] = sd == 0 ? m.ten_J[t * nv + lane] : -m.ten_J[t * nv + lane];
+        if (lane < nv) J[nefc * nv + lane] = sd == 0 ? ten_jac(m, s, t, lane) : -ten_jac(m, s, t, lane);
         if (lane == 0) {
           type[nefc] = __int_as_float(EFC_TLIMIT * 65536 + t);
           pos[nefc] = dist[sd]; marg[nefc] = mg; floss[nefc] = 0;
@@ -7380,6 +7441,13 @@ __device__ void sensors_more(ENV_PARAMS, gfloat* sensordata, int ncon) {
     gfloat* out = sensordata + __float_as_int(sr[2]);
     float cutoff = sr[4];
     float o0 = 0, o1 = 0, o2 = 0;
+    if (t == MRS_SENS_TENDONPOS || t == MRS_SENS_TENDONVEL) {
+      // mjSENS_TENDONPOS / TENDONVEL: the step's tendon slot (the tendon id is word 14)
+      o0 = s[L.ten + 2 * __float_as_int(sr[14]) + (t == MRS_SENS_TENDONVEL ? 1 : 0)];
+      if (cutoff > 0) o0 = clampf(o0, -cutoff, cutoff);
+      out[0] = o0;
+      continue;
+    }
     if (t == MRS_SENS_SUBTREECOM || t == MRS_SENS_SUBTREELINVEL) {
       const int e = __float_as_int(sr[15]);
       const float sm = body_subtreemass_env(m, scr, b, sr[20]);

@@ -1249,6 +1249,11 @@ struct Compiler {
         if (!get_str(e, cls, tag, "joint", objname)) fail(e, "sensor requires 'joint'");
         type = tag == "jointpos" ? MRS_SENS_JOINTPOS : MRS_SENS_JOINTVEL;
         dim = 1;
+      } else if (tag == "tendonpos" || tag == "tendonvel") {
+        objtype = MRS_OBJ_TENDON;
+        if (!get_str(e, cls, tag, "tendon", objname)) fail(e, "sensor requires 'tendon'");
+        type = tag == "tendonpos" ? MRS_SENS_TENDONPOS : MRS_SENS_TENDONVEL;
+        dim = 1;
       } else if (tag == "actuatorfrc") {
         objtype = MRS_OBJ_ACTUATOR;
         if (!get_str(e, cls, tag, "actuator", objname)) fail(e, "sensor requires 'actuator'");
@@ -1699,6 +1704,7 @@ struct Compiler {
     x0pos = c.xpos;
     x0quat = c.xquat;
     Minv0 = c.Minv;
+    ic0 = c;
     const std::vector<double>&xpos = c.xpos, &xquat = c.xquat, &xipos = c.xipos;
     // statistic: extent/center when not given (bounding box of body and geom positions at qpos0)
     if (!extent_given) {
@@ -1788,17 +1794,23 @@ struct Compiler {
   }
   std::vector<double> x0pos, x0quat;  // body poses at qpos0 (set0)
   std::vector<double> Minv0;          // M(qpos0)^-1, dense (set0)
-  // <tendon><fixed> [upstream mjCTendon, fixed only]: wraps of hinge / slide joints with coefficients;
-  // limited (autolimits: a range given), range, margin, solreflimit / solimplimit, frictionloss,
-  // solreffriction / solimpfriction, stiffness, damping, springlength (one value, two for a dead band;
-  // -1: the length at qpos_spring), tendon_invweight0 = J M(qpos0)^-1 J' [upstream mj_setConst]
+  setconst::InertialConst ic0;        // the kinematics at qpos0 (set0): spatial tendons' length0 and J
+  std::vector<double> tendon_J0;      // [ntendon][nv] the tendons' Jacobians at qpos0 (set0_actuators' dampratio)
+  // <tendon><fixed> / <spatial> [upstream mjCTendon]: a fixed tendon wraps hinge / slide joints with
+  // coefficients; a spatial one is a path of <site> children cut into branches by <pulley divisor>
+  // (geom wraps and sidesite are rejected).  Both take limited (autolimits: a range given), range,
+  // margin, solreflimit / solimplimit, frictionloss, solreffriction / solimpfriction, stiffness, damping,
+  // springlength (one value, two for a dead band; -1: the length at qpos_spring for a fixed tendon, at
+  // qpos0 for a spatial one [upstream uses qpos_spring for both; verify]); width / rgba / material are
+  // visual and ignored.  tendon_length0 and tendon_invweight0 = J M(qpos0)^-1 J' are taken at qpos0
+  // [upstream mj_setConst]
   void parse_tendons(const XmlElement* sec) {
     const int nv = m.nv;
     for (auto& cp : sec->children) {
       const XmlElement* e = cp.get();
       const std::string& tag = e->tag;
-      if (tag == "spatial") fail(e, "spatial tendons are not supported");
-      if (tag != "fixed") fail(e, "unsupported tendon type '" + tag + "'");
+      const bool spatial = tag == "spatial";
+      if (!spatial && tag != "fixed") fail(e, "unsupported tendon type '" + tag + "'");
       const DefaultClass* cls = resolve_class(e, "");
       double range[2] = {0, 0}, margin = 0, srl[2] = {0.02, 1}, sil[5] = {0.9, 0.95, 0.001, 0.5, 2};
       double fl = 0, srf[2] = {0.02, 1}, sif[5] = {0.9, 0.95, 0.001, 0.5, 2}, k = 0, b = 0, ls[2] = {-1, -1};
@@ -1832,22 +1844,70 @@ struct Compiler {
       const int adr = static_cast<int>(m.wrap_objid.size());
       double len_spring = 0, len0 = 0;
       std::vector<double> J(nv, 0.0);
-      for (auto& wp : e->children) {
-        const XmlElement* w = wp.get();
-        if (w->tag != "joint") fail(w, "fixed tendons wrap joints only");
-        std::string jn;
-        if (!get_str(w, nullptr, "joint", "joint", jn)) fail(w, "tendon joint requires 'joint'");
-        const int j = m.name2id(MRS_OBJ_JOINT, jn);
-        if (j < 0) fail(w, "unknown joint '" + jn + "'");
-        if (m.jnt_type[j] != MRS_JNT_HINGE && m.jnt_type[j] != MRS_JNT_SLIDE)
-          fail(w, "fixed tendons need hinge or slide joints");
-        double coef = 0;
-        if (!get_real(w, nullptr, "joint", "coef", coef)) fail(w, "tendon joint requires 'coef'");
-        m.wrap_objid.push_back(j);
-        m.wrap_prm.push_back(coef);
-        len_spring += coef * m.qpos_spring[m.jnt_qposadr[j]];
-        len0 += coef * m.qpos0[m.jnt_qposadr[j]];
-        J[m.jnt_dofadr[j]] += coef;
+      if (spatial) {
+        // the path's shape first (no name is resolved before it is known to be a path)
+        int nsites = 0, branch = 0;
+        bool pulley_last = false;
+        for (auto& wp : e->children) {
+          const XmlElement* w = wp.get();
+          if (w->tag == "geom") fail(w, "spatial tendons wrapping geoms (sphere / cylinder wrapping) are not supported");
+          if (w->tag == "site") {
+            ++nsites; ++branch;
+            pulley_last = false;
+          } else if (w->tag == "pulley") {
+            if (nsites == 0) fail(w, "a spatial tendon cannot start with a pulley");
+            if (pulley_last) fail(w, "a spatial tendon cannot have two pulleys in a row");
+            if (branch < 2) fail(w, "a branch of a spatial tendon needs at least two sites");
+            branch = 0;
+            pulley_last = true;
+          } else {
+            fail(w, "spatial tendons take site and pulley elements only");
+          }
+        }
+        if (nsites < 2) fail(e, "spatial tendons need at least two sites");
+        if (pulley_last) fail(e, "a spatial tendon cannot end with a pulley");
+        if (branch < 2) fail(e, "a branch of a spatial tendon needs at least two sites");
+        for (auto& wp : e->children) {
+          const XmlElement* w = wp.get();
+          std::string nm;
+          if (w->attr("sidesite")) fail(w, "sidesite is not supported (spatial tendons wrap no geoms)");
+          if (w->tag == "site") {
+            if (!get_str(w, nullptr, "site", "site", nm)) fail(w, "tendon site requires 'site'");
+            const int sid = m.name2id(MRS_OBJ_SITE, nm);
+            if (sid < 0) fail(w, "unknown site '" + nm + "'");
+            m.wrap_type.push_back(MRS_WRAP_SITE);
+            m.wrap_objid.push_back(sid);
+            m.wrap_prm.push_back(0);
+          } else {
+            double div = 0;
+            if (!get_real(w, nullptr, "pulley", "divisor", div)) fail(w, "tendon pulley requires 'divisor'");
+            if (!(div > 0)) fail(w, "pulley divisor must be positive");
+            m.wrap_type.push_back(MRS_WRAP_PULLEY);
+            m.wrap_objid.push_back(-1);
+            m.wrap_prm.push_back(div);
+          }
+        }
+        len0 = setconst::spatial_tendon0(m, ic0, adr, static_cast<int>(m.wrap_objid.size()) - adr, J);
+        len_spring = len0;
+      } else {
+        for (auto& wp : e->children) {
+          const XmlElement* w = wp.get();
+          if (w->tag != "joint") fail(w, "fixed tendons wrap joints only");
+          std::string jn;
+          if (!get_str(w, nullptr, "joint", "joint", jn)) fail(w, "tendon joint requires 'joint'");
+          const int j = m.name2id(MRS_OBJ_JOINT, jn);
+          if (j < 0) fail(w, "unknown joint '" + jn + "'");
+          if (m.jnt_type[j] != MRS_JNT_HINGE && m.jnt_type[j] != MRS_JNT_SLIDE)
+            fail(w, "fixed tendons need hinge or slide joints");
+          double coef = 0;
+          if (!get_real(w, nullptr, "joint", "coef", coef)) fail(w, "tendon joint requires 'coef'");
+          m.wrap_type.push_back(MRS_WRAP_JOINT);
+          m.wrap_objid.push_back(j);
+          m.wrap_prm.push_back(coef);
+          len_spring += coef * m.qpos_spring[m.jnt_qposadr[j]];
+          len0 += coef * m.qpos0[m.jnt_qposadr[j]];
+          J[m.jnt_dofadr[j]] += coef;
+        }
       }
       const int num = static_cast<int>(m.wrap_objid.size()) - adr;
       if (num == 0) fail(e, "a fixed tendon needs at least one joint");
@@ -1859,6 +1919,8 @@ struct Compiler {
         for (int jj = 0; jj < nv; ++jj) iw += J[i] * Minv0[i * nv + jj] * J[jj];
       m.tendon_adr.push_back(adr);
       m.tendon_num.push_back(num);
+      m.tendon_kind.push_back(spatial ? MRS_TENDON_SPATIAL : MRS_TENDON_FIXED);
+      tendon_J0.insert(tendon_J0.end(), J.begin(), J.begin() + nv);
       m.tendon_limited.push_back(lim);
       m.tendon_range.insert(m.tendon_range.end(), range, range + 2);
       m.tendon_margin.push_back(margin);
@@ -2090,10 +2152,18 @@ struct Compiler {
       double gear = m.actuator_gear[6 * a];
       double mass = 0;
       if (m.actuator_trntype[a] == MRS_TRN_TENDON) {
-        // moment gear * coef on each wrapped dof
-        for (int k = m.tendon_adr[j]; k < m.tendon_adr[j] + m.tendon_num[j]; ++k) {
-          const double mo = gear * m.wrap_prm[k];
-          if (mo != 0) mass += m.dof_M0[m.jnt_dofadr[m.wrap_objid[k]]] / (mo * mo);
+        if (m.tendon_kind[j] == MRS_TENDON_SPATIAL) {
+          // moment gear * J(qpos0) on each dof it moves
+          for (int d = 0; d < m.nv; ++d) {
+            const double mo = gear * tendon_J0[static_cast<size_t>(j) * m.nv + d];
+            if (mo != 0) mass += m.dof_M0[d] / (mo * mo);
+          }
+        } else {
+          // moment gear * coef on each wrapped dof
+          for (int k = m.tendon_adr[j]; k < m.tendon_adr[j] + m.tendon_num[j]; ++k) {
+            const double mo = gear * m.wrap_prm[k];
+            if (mo != 0) mass += m.dof_M0[m.jnt_dofadr[m.wrap_objid[k]]] / (mo * mo);
+          }
         }
       } else {
         int d = m.jnt_dofadr[j];
@@ -2203,6 +2273,7 @@ mrs_model_view Model::view() const {
   MRS_V(actuator_dynprm); MRS_V(actuator_actrange); MRS_V(key_act);
   v.nmocap = nmocap;
   MRS_V(body_mocapid); MRS_V(key_mpos); MRS_V(key_mquat);
+  MRS_V(wrap_type); MRS_V(tendon_kind);
 #undef MRS_V
   return v;
 }

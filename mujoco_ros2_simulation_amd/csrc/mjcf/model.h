@@ -81,8 +81,8 @@ struct Model {
   // equality constraints (mrs_model_view eq_*)
   std::vector<int> eq_type, eq_obj1id, eq_obj2id, eq_active0;
   std::vector<double> eq_solref, eq_solimp, eq_data;
-  // fixed tendons (mrs_model_view tendon_* / wrap_*)
-  std::vector<int> tendon_adr, tendon_num, tendon_limited, wrap_objid;
+  // fixed and spatial tendons (mrs_model_view tendon_* / wrap_*)
+  std::vector<int> tendon_adr, tendon_num, tendon_limited, wrap_objid, wrap_type, tendon_kind;
   std::vector<double> wrap_prm, tendon_range, tendon_margin, tendon_solref_lim, tendon_solimp_lim,
       tendon_frictionloss, tendon_solref_fri, tendon_solimp_fri, tendon_stiffness, tendon_damping,
       tendon_lengthspring, tendon_invweight0, tendon_length0;

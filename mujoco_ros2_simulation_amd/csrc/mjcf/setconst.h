@@ -112,6 +112,7 @@ struct InertialConst {
   double meaninertia = 1;
   std::vector<double> xpos, xquat, xipos;  // body frames and inertial-frame origins at qpos0
   std::vector<double> Minv;                // M(qpos0)^-1, dense [nv][nv]
+  std::vector<double> scom, cdof;          // subtree coms [nbody][3] and motion axes about them [nv][6] at qpos0
 };
 
 // The constants of model m with body_mass [nbody], body_inertia [nbody][3] and dof_armature [nv]
@@ -164,7 +165,8 @@ inline void derive_inertial(const Model& m, const double* body_mass, const doubl
     quat2mat(&ximat[9 * b], iq);
   }
   // subtree com
-  std::vector<double> scom(3 * nb, 0);
+  std::vector<double>& scom = out.scom;
+  scom.assign(3 * nb, 0);
   for (int b = 0; b < nb; ++b)
     for (int i = 0; i < 3; ++i) scom[3 * b + i] = body_mass[b] * xipos[3 * b + i];
   for (int b = nb - 1; b > 0; --b)
@@ -173,7 +175,8 @@ inline void derive_inertial(const Model& m, const double* body_mass, const doubl
     for (int i = 0; i < 3; ++i)
       scom[3 * b + i] = body_subtreemass[b] > kMinVal ? scom[3 * b + i] / body_subtreemass[b] : xipos[3 * b + i];
   // cdof
-  std::vector<double> cdof(6 * std::max(1, nv), 0);
+  std::vector<double>& cdof = out.cdof;
+  cdof.assign(6 * std::max(1, nv), 0);
   for (int j = 0; j < m.njnt; ++j) {
     int b = m.jnt_bodyid[j], d = m.jnt_dofadr[j];
     const double* c = &scom[3 * m.body_rootid[b]];
@@ -279,6 +282,56 @@ inline void derive_inertial(const Model& m, const double* body_mass, const doubl
     out.body_invweight0[2 * b] = t;
     out.body_invweight0[2 * b + 1] = r;
   }
+}
+
+// translational Jacobian [3][nv] at qpos0 of the world point p on body b (mj_jac's jacp): the columns of
+// the dofs of b and its ancestors, cdof's linear part plus its angular part crossed with the offset from
+// the tree's com
+inline void point_jacp(const Model& m, const InertialConst& c, int b, const double p[3], std::vector<double>& jacp) {
+  const int nv = m.nv;
+  jacp.assign(3 * std::max(1, nv), 0.0);
+  double off[3];
+  for (int i = 0; i < 3; ++i) off[i] = p[i] - c.scom[3 * m.body_rootid[b] + i];
+  for (int x = b; x != 0; x = m.body_parentid[x])
+    for (int j = m.body_dofadr[x]; j < m.body_dofadr[x] + m.body_dofnum[x]; ++j) {
+      double cr[3];
+      cross3(cr, &c.cdof[6 * j], off);
+      for (int i = 0; i < 3; ++i) jacp[i * nv + j] = c.cdof[6 * j + 3 + i] + cr[i];
+    }
+}
+
+// mj_tendon at qpos0 for a path of sites and pulleys (wraps [adr, adr + num) of m.wrap_*): the length
+// sum_seg w |p1 - p0| and the Jacobian sum_seg w dir' (jacp(site1) - jacp(site0)) [nv], w = 1 / divisor
+// of the last pulley before the segment (1 before the first); a segment within one body adds length only
+inline double spatial_tendon0(const Model& m, const InertialConst& c, int adr, int num, std::vector<double>& J) {
+  const int nv = m.nv;
+  J.assign(std::max(1, nv), 0.0);
+  double len = 0, w = 1;
+  auto site_world = [&](int sid, double p[3]) {
+    const int b = m.site_bodyid[sid];
+    rot_vec_quat(p, &m.site_pos[3 * sid], &c.xquat[4 * b]);
+    for (int i = 0; i < 3; ++i) p[i] += c.xpos[3 * b + i];
+  };
+  std::vector<double> j0, j1;
+  for (int k = adr; k < adr + num; ++k) {
+    if (m.wrap_type[k] == MRS_WRAP_PULLEY) { w = 1 / m.wrap_prm[k]; continue; }
+    if (k + 1 >= adr + num || m.wrap_type[k + 1] != MRS_WRAP_SITE) continue;
+    const int s0 = m.wrap_objid[k], s1 = m.wrap_objid[k + 1];
+    double p0[3], p1[3], d[3];
+    site_world(s0, p0);
+    site_world(s1, p1);
+    for (int i = 0; i < 3; ++i) d[i] = p1[i] - p0[i];
+    const double n = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    len += w * n;
+    if (m.site_bodyid[s0] == m.site_bodyid[s1]) continue;
+    if (n < kMinVal) { d[0] = 1; d[1] = d[2] = 0; }  // (mju_normalize3 of a null vector)
+    else for (int i = 0; i < 3; ++i) d[i] /= n;
+    point_jacp(m, c, m.site_bodyid[s0], p0, j0);
+    point_jacp(m, c, m.site_bodyid[s1], p1, j1);
+    for (int j = 0; j < nv; ++j)
+      for (int i = 0; i < 3; ++i) J[j] += w * d[i] * (j1[i * nv + j] - j0[i * nv + j]);
+  }
+  return len;
 }
 
 }  // namespace setconst

@@ -31,6 +31,7 @@ SENS_ACCELEROMETER, SENS_GYRO, SENS_FORCE, SENS_TORQUE, SENS_RANGEFINDER = 1, 3,
 SENS_JOINTPOS, SENS_JOINTVEL, SENS_ACTUATORFRC, SENS_FRAMEPOS, SENS_FRAMEQUAT = 9, 10, 15, 25, 26
 SENS_TOUCH, SENS_VELOCIMETER, SENS_FRAMEXAXIS, SENS_FRAMEYAXIS, SENS_FRAMEZAXIS = 0, 2, 27, 28, 29
 SENS_FRAMELINVEL, SENS_FRAMEANGVEL, SENS_FRAMELINACC, SENS_SUBTREECOM, SENS_SUBTREELINVEL = 30, 31, 32, 34, 35
+SENS_TENDONPOS, SENS_TENDONVEL = 11, 12
 BIAS_NONE, BIAS_AFFINE = 0, 1
 RESTATE_NEWTON_REFINE, RESTATE_PGS_ELLIPTIC_BLOCK, RESTATE_NO_MPR_POLISH, RESTATE_NO_MULTICCD = 1, 2, 4, 8
 (FIELD_QPOS, FIELD_QVEL, FIELD_CTRL, FIELD_QFRC_APPLIED, FIELD_QACC_WARMSTART, FIELD_QACC,
@@ -175,6 +176,11 @@ DYN_NONE, DYN_INTEGRATOR, DYN_FILTER, DYN_FILTEREXACT = range(4)
 _MOCAP_SIZES = ["nmocap"]
 _MOCAP_ARRAYS = [("body_mocapid", "i", "nbody", 1), ("key_mpos", "d", "nkey", ("nmocap", 3)),
                  ("key_mquat", "d", "nkey", ("nmocap", 4))]
+# tendon paths (after the mocap block): each wrap's type, each tendon's kind.  A fixed tendon's wraps are
+# joints (wrap_prm the coefficient), a spatial one's sites and pulleys (wrap_prm the divisor)
+_PATH_ARRAYS = [("wrap_type", "i", "nwrap", 1), ("tendon_kind", "i", "ntendon", 1)]
+WRAP_NONE, WRAP_JOINT, WRAP_PULLEY, WRAP_SITE = range(4)
+TENDON_FIXED, TENDON_SPATIAL = 0, 1
 
 
 class ModelView(C.Structure):
@@ -201,7 +207,8 @@ class ModelView(C.Structure):
                 [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _SITE_ARRAYS] +
                 [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _ACT_ARRAYS] +
                 [(n, C.c_int) for n in _MOCAP_SIZES] +
-                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _MOCAP_ARRAYS])
+                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _MOCAP_ARRAYS] +
+                [(n, C.POINTER(C.c_int) if k == "i" else C.POINTER(C.c_double)) for n, k, _, _ in _PATH_ARRAYS])
 
 
 _lib = None
@@ -347,7 +354,7 @@ class Model:
         self.vis_headlight = np.array(v.vis_headlight[:])
         for name, kind, count, width in (_ARRAYS + _MESH_ARRAYS + _CONTACT_ARRAYS + _EQ_ARRAYS + _REND_ARRAYS +
                                          _TEN_ARRAYS + _POLY_ARRAYS + _SITE_ARRAYS + _ACT_ARRAYS +
-                                         _MOCAP_ARRAYS):
+                                         _MOCAP_ARRAYS + _PATH_ARRAYS):
             n = getattr(v, count)
             if isinstance(width, tuple):
                 w = getattr(v, width[0]) * width[1]
