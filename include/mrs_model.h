@@ -37,7 +37,7 @@ enum { MRS_TEX_2D = 0, MRS_TEX_CUBE = 1, MRS_TEX_SKYBOX = 2 };  /* mjtTexture */
 enum { MRS_BUILTIN_NONE = 0, MRS_BUILTIN_GRADIENT = 1, MRS_BUILTIN_CHECKER = 2, MRS_BUILTIN_FLAT = 3 };
 enum { MRS_MARK_NONE = 0, MRS_MARK_EDGE = 1, MRS_MARK_CROSS = 2 };
 #define MRS_NEQDATA 11
-enum { MRS_TRN_JOINT = 0, MRS_TRN_TENDON = 3 };
+enum { MRS_TRN_JOINT = 0, MRS_TRN_TENDON = 3, MRS_TRN_SITE = 4 };  /* mjtTrn subset */
 enum { MRS_WRAP_NONE = 0, MRS_WRAP_JOINT = 1, MRS_WRAP_PULLEY = 2, MRS_WRAP_SITE = 3 };  /* mjtWrap subset */
 enum { MRS_TENDON_FIXED = 0, MRS_TENDON_SPATIAL = 1 };  /* tendon_kind (this project's own) */
 enum { MRS_DYN_NONE = 0, MRS_DYN_INTEGRATOR = 1, MRS_DYN_FILTER = 2, MRS_DYN_FILTEREXACT = 3 };
@@ -120,7 +120,10 @@ typedef struct mrs_model_view {
   const int *cam_bodyid, *cam_resolution /*2*/;
   const double *cam_pos /*3*/, *cam_quat /*4*/, *cam_fovy;
 
-  /* actuators */
+  /* actuators.  actuator_trntype MRS_TRN_*, actuator_trnid[0] the joint, tendon or site.  A joint or
+   * tendon transmission uses gear[0]; a site transmission (MRS_TRN_SITE, mjTRN_SITE without refsite) all
+   * six: force gear[0:3] and torque gear[3:6] per unit of actuator force, in the site's frame, on the
+   * site's body at the site -- length 0, velocity moment . qvel */
   const int *actuator_trntype, *actuator_dyntype, *actuator_gaintype, *actuator_biastype,
       *actuator_trnid /*2*/, *actuator_ctrllimited, *actuator_forcelimited;
   const double *actuator_gear /*6*/, *actuator_gainprm /*10*/, *actuator_biasprm /*10*/,

@@ -473,7 +473,7 @@ BatchImpl* batch_create(const Model* model, int n_envs, int device, int max_cont
       prod.rf_sweep = 0;  // (the producer pass is a block pass over the static geoms)
       DevModel* d_prod = static_cast<DevModel*>(dalloc(*b, sizeof(DevModel)));
       HIP_CHECK(hipMemcpyAsync(d_prod, &prod, sizeof(DevModel), hipMemcpyHostToDevice, b->stream));
-      HIP_CHECK(launch_step(d_prod, b->L.total, b->dm.shr_total, b->st, 1, 1, true, b->group, false, b->ext, false, false, b->stream));
+      HIP_CHECK(launch_step(d_prod, b->L.total, b->dm.shr_total, b->st, 1, 1, true, b->group, false, b->ext, b->dm.nact_site > 0, false, b->stream));
       HIP_CHECK(hipStreamSynchronize(b->stream));
     }
     batch_launch(b, 1, true);  // mj_forward after load (src/mujoco_system_interface.cpp:741)
@@ -844,8 +844,10 @@ void batch_launch(BatchImpl* b, int n_steps, bool forward_only) {
   if (timed) HIP_CHECK(hipEventRecord(b->ev0[0], b->stream));
   DevState st = b->st;
   if (b->ctrl_bound) st.ctrl = const_cast<float*>(b->ctrl_bound);  // (read only: loaded at launch start)
+  // (a model with site actuators takes the parameter parts, which alone carry their code: DESIGN.md §3.24)
   HIP_CHECK(launch_step(b->d_dm, b->L.total, b->dm.shr_total, st, b->n, n_steps, forward_only, b->group,
-                        b->model->solver != MRS_SOL_PGS, b->ext, b->dm.prm_mask != 0, b->dm.dyn_mask != 0, b->stream));
+                        b->model->solver != MRS_SOL_PGS, b->ext, b->dm.prm_mask != 0 || b->dm.nact_site > 0,
+                        b->dm.dyn_mask != 0, b->stream));
   if (timed) HIP_CHECK(hipEventRecord(b->ev1[0], b->stream));
   b->ev_valid[0] = timed;
 }

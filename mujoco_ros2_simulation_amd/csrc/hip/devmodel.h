@@ -310,6 +310,18 @@ struct DevModel {
   int nten_spatial, lds_tenJ;
   CPtr<int> tsp_ten, tsp_adr, tsp_num, ten_sp;
   CPtr<float> tsp_seg;
+  // site actuators (MRS_TRN_SITE; devtables.h actuator_tables): their count -- 0 for
+  // every model without one; a model with one launches the MRS_PRM parts, which alone carry their code
+  // (step_dispatch.hip launch_step) -- and how many of them have a
+  // length or velocity term (an affine gain or bias with prm[1] or prm[2] set).  Site actuator k has the
+  // 12-float record sact[12 k]: the actuator and the site's body (int bits), the site's position in the
+  // body's frame [3], the site's local rotation applied to the gear's force [3] and torque [3] halves,
+  // pad.  Its length (0) and velocity moment . qvel of the step go to slot ntendon + k of L.ten, which
+  // such a model sizes for ntendon + nact_site entries (plan.h lds_layout); its actrec addresses point
+  // there and its actrec gear is 1 (the gear is in the moment).  Kept last: the fields above keep
+  // their offsets
+  int nact_site, nact_site_vel;
+  CPtr<float> sact;
 };
 constexpr int kRayBlock = 128;
 // bits of DevModel::prm_mask (1 << MRS_PARAM_*)

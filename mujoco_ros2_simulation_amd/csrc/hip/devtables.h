@@ -658,14 +658,45 @@ inline RowLists row_lists(const Model& m, const PairTables& pairs, int max_con_r
 
 // actuators: joint transmissions by dof / qpos address; a tendon transmission's addresses hold
 // -1 - tendon (length and velocity from the step's tendon slot in LDS), its moment is gear * ten_J
+// A site transmission (DevModel::nact_site) has a record in `site` (12 floats: the actuator, the site's
+// body, the site's local position, the gear's force and torque halves turned into the body's frame); its
+// addresses hold -1 - (ntendon + k), the slot behind the tendons' that step.hip site_act_vel fills, and
+// its gear here is 1: the six gear numbers are in the moment
 struct ActTables {
   std::vector<int> dof, qadr, ten;
-  std::vector<float> gear, gain, bias;
+  std::vector<float> gear, gain, bias, site;
 };
-inline ActTables actuator_tables(const Model& m) {
+inline ActTables actuator_tables(const Model& m, DevModel& d) {
   ActTables t;
+  const int ntendon = static_cast<int>(m.tendon_adr.size());
+  d.nact_site = d.nact_site_vel = 0;
   for (int a = 0; a < m.nu; ++a) {
     int j = m.actuator_trnid[2 * a];
+    if (m.actuator_trntype[a] == MRS_TRN_SITE) {
+      const int slot = ntendon + d.nact_site++;
+      t.dof.push_back(-1 - slot);
+      t.qadr.push_back(-1 - slot);
+      t.ten.push_back(-1);
+      double R[9];
+      quat_to_mat(&m.site_quat[4 * j], R);
+      const double* g = &m.actuator_gear[6 * a];
+      t.site.insert(t.site.end(), {int_bits(a), int_bits(m.site_bodyid[j]), static_cast<float>(m.site_pos[3 * j]),
+                                   static_cast<float>(m.site_pos[3 * j + 1]), static_cast<float>(m.site_pos[3 * j + 2])});
+      for (int h = 0; h < 2; ++h)
+        for (int i = 0; i < 3; ++i)
+          t.site.push_back(static_cast<float>(R[3 * i] * g[3 * h] + R[3 * i + 1] * g[3 * h + 1] + R[3 * i + 2] * g[3 * h + 2]));
+      t.site.push_back(0.0f);
+      const double *gp = &m.actuator_gainprm[MRS_NGAIN * a], *bp = &m.actuator_biasprm[MRS_NBIAS * a];
+      if ((m.actuator_gaintype[a] == MRS_GAIN_AFFINE && (gp[1] != 0 || gp[2] != 0)) ||
+          (m.actuator_biastype[a] == MRS_BIAS_AFFINE && (bp[1] != 0 || bp[2] != 0)))
+        ++d.nact_site_vel;
+      t.gear.push_back(1.0f);
+      for (int i = 0; i < 3; ++i) {
+        t.gain.push_back(static_cast<float>(gp[i]));
+        t.bias.push_back(static_cast<float>(bp[i]));
+      }
+      continue;
+    }
     if (m.actuator_trntype[a] == MRS_TRN_TENDON) {
       t.dof.push_back(-1 - j);
       t.qadr.push_back(-1 - j);
@@ -1122,7 +1153,7 @@ inline DevTables build_tables(const Model& m, int max_con_req, const Overrides& 
   d.xrows = d.neq + d.nten_fric + d.nten_lim;
   const KinTrees kt = kinematic_trees(m, pairs, d);
   const RowLists rows = row_lists(m, pairs, max_con_req, d);
-  const ActTables act = actuator_tables(m);
+  const ActTables act = actuator_tables(m, d);
 
   T.addi(&D::body_parentid, m.body_parentid); T.addi(&D::body_rootid, m.body_rootid);
   T.addi(&D::body_jntnum, m.body_jntnum); T.addi(&D::body_jntadr, m.body_jntadr);
@@ -1221,6 +1252,8 @@ inline DevTables build_tables(const Model& m, int max_con_req, const Overrides& 
     T.addi(&D::tsp_ten, ten.sp_ten); T.addi(&D::tsp_adr, ten.sp_adr); T.addi(&D::tsp_num, ten.sp_num);
     T.addi(&D::ten_sp, ten.sp_of); T.addf(&D::tsp_seg, ten.sp_seg);
   }
+  // site actuators, likewise after every table a model without one has
+  if (d.nact_site > 0) T.addf(&D::sact, act.site);
   return T;
 }
 

@@ -34,7 +34,9 @@ inline LdsLayout lds_layout(const Model& m, const DevModel& d, bool blocked, boo
   L.qfrc_passive = take(nv); L.qfrc_act = take(nv); L.qfrc_smooth = take(nv); L.qacc_smooth = take(nv);
   L.qacc = take(nv + 1); L.qfrc_con = take(nv + 1);  // + a dummy word (blocked-mode solver)
   L.act_force = take(std::max(1, m.nu));
-  L.ten = d.ntendon > 0 ? take(2 * d.ntendon) : 0;  // tendon lengths and velocities of the step
+  // tendon lengths and velocities of the step; behind them the site actuators' (DevModel::nact_site: 0
+  // and their velocity, slot ntendon + k), which only a model with a site actuator takes
+  L.ten = d.ntendon + d.nact_site > 0 ? take(2 * (d.ntendon + d.nact_site)) : 0;
   L.niter = take(1);
   L.hcon = take(1);
   L.Lh = want_lh ? take(nv * nv) : 0;

@@ -2590,6 +2590,65 @@ __device__ __attribute__((noinline)) void spatial_tendons(ENV_PARAMS) {
   wsync();
 }
 
+// ---- site actuators (mj_transmission's mjTRN_SITE branch without refsite).  Both
+// phases are out of line and reached only behind the scalar test m.nact_site > 0 inside smooth_forces,
+// and the test and the calls are compiled into the MRS_PRM parts alone (kSiteAct), which launch_step
+// takes for a model with a site actuator as it does for a batch with a per-env parameter: every other
+// part carries none of this, not even the test.
+constexpr bool kSiteAct = kPrm;
+
+// site actuator r's moment on dof j at the env's pose: R_b glin . jacp_j(b, p) + R_b grot . jacr_j(b), p
+// the site's world position on its body b, glin / grot the gear's halves in b's frame (record
+// DevModel::sact); jacr_j is the angular half of cdof_j when dof j moves b, and zero otherwise (a site on
+// the world, or welded to it, gets zero altogether)
+__device__ __forceinline__ float site_moment(const DevModel& m, const lfloat* s, const CPtr<float> r, int j) {
+  const LdsLayout& L = m.L;
+  const int b = __float_as_int(r[1]), bj = m.dof_bodyid[j];
+  if (!(b >= bj && b < m.body_subtree_end[bj])) return 0.0f;
+  const float lp[3] = {r[2], r[3], r[4]}, gl[3] = {r[5], r[6], r[7]}, gr[3] = {r[8], r[9], r[10]};
+  float R[9], p[3], wl[3], wr[3], col[3];
+  for (int i = 0; i < 9; ++i) R[i] = s[L.xmat + 9 * b + i];
+  mat_vec(p, R, lp);
+  for (int i = 0; i < 3; ++i) p[i] += s[L.xpos + 3 * b + i];
+  mat_vec(wl, R, gl);
+  mat_vec(wr, R, gr);
+  jac_col(m, s, b, p, j, col);
+  const float ang[3] = {s[L.cdof + 6 * j], s[L.cdof + 6 * j + 1], s[L.cdof + 6 * j + 2]};
+  return dot3(wl, col) + dot3(wr, ang);
+}
+// phase (a), before the actuator-force loop: each site actuator's length 0 and velocity moment . qvel
+// (one group sum per actuator) into its slot behind the tendons', which the force loop reads through the
+// actuator's addresses.  Without a length or velocity term on any of them -- none in the model, and no
+// per-env gain / bias rows that could bring one -- the moments are not formed and the slots get zeros
+template <int G>
+__device__ __attribute__((noinline)) void site_act_vel(ENV_PARAMS) {
+  ENV_UNPACK;
+  const bool need = m.nact_site_vel > 0 || (kPrm && (m.prm_mask & (kPrmGain | kPrmBias)));
+  #pragma unroll 1
+  for (int k = 0; k < m.nact_site; ++k) {
+    float vel = 0;
+    if (need) vel = gsum<G>(lane < m.nv ? site_moment(m, s, m.sact + 12 * k, lane) * s[L.qvel + lane] : 0.0f);
+    if (lane == 0) { s[L.ten + 2 * (m.ntendon + k)] = 0; s[L.ten + 2 * (m.ntendon + k) + 1] = vel; }
+  }
+  wsync();
+}
+// phase (b), where qfrc_actuator is assembled: the lane's dof gets sum_a force_a moment_{a,j} over the
+// site actuators, which smooth_forces adds to the dof's joint and tendon actuators before the joint's
+// actuatorfrcrange clamp
+template <int G>
+__device__ __attribute__((noinline)) float site_act_qfrc(ENV_PARAMS) {
+  ENV_UNPACK;
+  float q = 0;
+  if (lane < m.nv) {
+    #pragma unroll 1
+    for (int k = 0; k < m.nact_site; ++k) {
+      const CPtr<float> r = m.sact + 12 * k;
+      q += s[L.act_force + __float_as_int(r[0])] * site_moment(m, s, r, lane);
+    }
+  }
+  return q;
+}
+
 // mj_passive + mj_fwdActuation + qfrc_smooth + qacc_smooth (lane per dof).  defer (forward(): 16-lane
 // PGS kernels with DevModel::solve_fuse): qacc_smooth is left to constraints(), which solves it with its
 // friction-loss rows or, on the dense path, by the same call as here; the lane's qfrc_smooth is returned
@@ -2614,6 +2673,9 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS, bool defer = false) {
     // spatial tendons (no wraps above: zeros so far): their length, velocity and Jacobian row at this pose
     if (m.nten_spatial > 0) { [[clang::noinline]] spatial_tendons<G>(ENV_ARGS); }
   }
+  // site actuators: their length (0) and velocity at this pose into the slots behind the tendons'
+  const bool site_acts = kSiteAct && m.nact_site > 0;
+  if (site_acts) { [[clang::noinline]] site_act_vel<G>(ENV_ARGS); }
   // actuator forces (lane per actuator)
   #pragma unroll 1
   for (int a = lane; a < m.nu; a += G) {
@@ -2652,6 +2714,9 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS, bool defer = false) {
   // sets a wrench pays this scalar branch alone
   float qx = 0;
   if (m.xfrc) { [[clang::noinline]] qx = xfrc_qfrc<G>(ENV_ARGS); }
+  // the site actuators' part of qfrc_actuator
+  float qsite = 0;
+  if (site_acts) { [[clang::noinline]] qsite = site_act_qfrc<G>(ENV_ARGS); }
   float qfs = 0;
   if (lane < nv) {
     const int j = lane;
@@ -2668,6 +2733,7 @@ __device__ MRS_PHASE float smooth_forces(ENV_PARAMS, bool defer = false) {
           qa += m.act_gear[a] * s[L.act_force + a] * ten_jac(m, s, m.act_ten[a], j);  // moment gear * J
       }
     }
+    if (site_acts) qa += qsite;
     if (__float_as_int(dr[2])) qa = clampf(qa, dr[3], dr[4]);
     s[L.qfrc_act + j] = qa;
     float pas = 0;

@@ -18,7 +18,8 @@ int phase_cycles(double* out, int n, bool reset) {
 #endif
 
 // The one rule that picks a part.  ext: the model needs the extended code; params: a per-env model
-// parameter is in use (DevModel::prm_mask != 0); dyn: a dynamics output is on (DevModel::dyn_mask != 0).
+// parameter is in use (DevModel::prm_mask != 0) or the model has a site actuator (DevModel::nact_site > 0,
+// whose code the parameter parts alone carry); dyn: a dynamics output is on (DevModel::dyn_mask != 0).
 // The parameter parts carry the outputs too.  With an output on and no parameter, the common layouts
 // have parts with the outputs alone (G = 16 without the extended code, with and without helper waves,
 // and G = 64 without it); every other one (G = 8, G = 32, a model that needs the extended code) takes

@@ -1076,9 +1076,22 @@ struct Compiler {
       if (tag != "motor" && tag != "position" && tag != "velocity" && tag != "general" && tag != "intvelocity")
         fail(e, "unsupported actuator type");
       const DefaultClass* cls = resolve_class(e, "");
-      std::string joint, tendon;
+      std::string joint, tendon, site;
       int jid, trn = MRS_TRN_JOINT;
-      if (get_str(e, cls, tag, "joint", joint)) {
+      // a site transmission (mjTRN_SITE without refsite): the actuator pushes and twists the site's body
+      // along the gear's six numbers in the site's frame
+      std::string other;
+      if (get_str(e, cls, tag, "site", site)) {
+        if (get_str(e, cls, tag, "refsite", other)) fail(e, "refsite is not supported");
+        // (with site= these name another transmission; beside joint= / tendon= they stay ignored as before)
+        for (const char* k : {"body", "jointinparent", "cranksite", "slidersite"})
+          if (get_str(e, cls, tag, k, other)) fail(e, "only joint and tendon transmissions are supported");
+        if (get_str(e, cls, tag, "joint", other) || get_str(e, cls, tag, "tendon", other))
+          fail(e, "an actuator takes one transmission: 'site' cannot be combined with 'joint' or 'tendon'");
+        jid = m.name2id(MRS_OBJ_SITE, site);
+        if (jid < 0) fail(e, "unknown site '" + site + "'");
+        trn = MRS_TRN_SITE;
+      } else if (get_str(e, cls, tag, "joint", joint)) {
         jid = m.name2id(MRS_OBJ_JOINT, joint);
         if (jid < 0) fail(e, "unknown joint '" + joint + "'");
       } else if (get_str(e, cls, tag, "tendon", tendon)) {
@@ -1180,6 +1193,11 @@ struct Compiler {
       if (trn == MRS_TRN_TENDON && m.integrator != MRS_INT_EULER && m.integrator != MRS_INT_RK4 &&
           (biastype == MRS_BIAS_AFFINE || gaintype == MRS_GAIN_AFFINE))
         fail(e, "velocity-dependent actuators on tendons are supported with the Euler and RK4 integrators only");
+      // (a site's moment depends on the pose: the implicit integrators would need its part of qDeriv.  A
+      // dampratio, still in biasprm[2] here, becomes a velocity gain)
+      if (trn == MRS_TRN_SITE && m.integrator != MRS_INT_EULER && m.integrator != MRS_INT_RK4 &&
+          ((biastype == MRS_BIAS_AFFINE && bias[2] != 0) || (gaintype == MRS_GAIN_AFFINE && gain[2] != 0)))
+        fail(e, "velocity-dependent actuators on sites are supported with the Euler and RK4 integrators only");
       m.actuator_trntype.push_back(trn);
       m.actuator_dyntype.push_back(dyntype);
       m.actuator_actadr.push_back(dyntype == MRS_DYN_NONE ? -1 : m.na);
@@ -2165,6 +2183,12 @@ struct Compiler {
             if (mo != 0) mass += m.dof_M0[m.jnt_dofadr[m.wrap_objid[k]]] / (mo * mo);
           }
         }
+      } else if (m.actuator_trntype[a] == MRS_TRN_SITE) {
+        // the site's moment at qpos0 on each dof it moves
+        std::vector<double> mom;
+        setconst::site_moment0(m, ic0, j, &m.actuator_gear[6 * a], mom);
+        for (int d = 0; d < m.nv; ++d)
+          if (mom[d] != 0) mass += m.dof_M0[d] / (mom[d] * mom[d]);
       } else {
         int d = m.jnt_dofadr[j];
         if ((m.jnt_type[j] == MRS_JNT_HINGE || m.jnt_type[j] == MRS_JNT_SLIDE) && gear != 0)

@@ -334,5 +334,28 @@ inline double spatial_tendon0(const Model& m, const InertialConst& c, int adr, i
   return len;
 }
 
+// mj_transmission's mjTRN_SITE branch (no refsite) at qpos0: the moment [nv] of an actuator on site sid
+// with the six gear numbers g in the site's frame, moment_j = R g[0:3] . jacp_j + R g[3:6] . jacr_j --
+// jacp of the site's world position on its body, jacr the angular half of cdof for the dofs of that
+// body and its ancestors.  A site on the world (or welded to it) gets zeros
+inline void site_moment0(const Model& m, const InertialConst& c, int sid, const double g[6], std::vector<double>& mom) {
+  const int nv = m.nv, b = m.site_bodyid[sid];
+  mom.assign(std::max(1, nv), 0.0);
+  double p[3], l[3], wl[3], wr[3];
+  rot_vec_quat(p, &m.site_pos[3 * sid], &c.xquat[4 * b]);
+  for (int i = 0; i < 3; ++i) p[i] += c.xpos[3 * b + i];
+  rot_vec_quat(l, g, &m.site_quat[4 * sid]);
+  rot_vec_quat(wl, l, &c.xquat[4 * b]);
+  rot_vec_quat(l, g + 3, &m.site_quat[4 * sid]);
+  rot_vec_quat(wr, l, &c.xquat[4 * b]);
+  std::vector<double> jacp;
+  point_jacp(m, c, b, p, jacp);
+  for (int j = 0; j < nv; ++j)
+    for (int i = 0; i < 3; ++i) mom[j] += wl[i] * jacp[i * nv + j];
+  for (int x = b; x != 0; x = m.body_parentid[x])
+    for (int j = m.body_dofadr[x]; j < m.body_dofadr[x] + m.body_dofnum[x]; ++j)
+      for (int i = 0; i < 3; ++i) mom[j] += wr[i] * c.cdof[6 * j + i];
+}
+
 }  // namespace setconst
 }  // namespace mrs

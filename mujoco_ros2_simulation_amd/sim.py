@@ -154,7 +154,7 @@ _TEN_ARRAYS = [
     ("tendon_lengthspring", "d", "ntendon", 2), ("tendon_invweight0", "d", "ntendon", 1),
     ("tendon_length0", "d", "ntendon", 1),
 ]
-TRN_JOINT, TRN_TENDON = 0, 3
+TRN_JOINT, TRN_TENDON, TRN_SITE = 0, 3, 4
 # mesh hull polygons (after the tendon block)
 _POLY_SIZES = ["nmeshpoly", "nmeshpolyvert"]
 _POLY_ARRAYS = [

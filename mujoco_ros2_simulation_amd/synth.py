@@ -67,7 +67,9 @@ def action_params(model: "sim.Model", env_ids: np.ndarray):
     half = np.full(model.nu, 0.5)
     for a in range(model.nu):
         j = model.actuator_trnid[a, 0]
-        if model.actuator_type(a) == sim.ACT_POSITION:
+        # (a position servo on a joint swings about the joint's qpos0; trnid of a tendon or site
+        # transmission is no joint id, and its length at qpos0 is not the centre: those stay at 0)
+        if model.actuator_type(a) == sim.ACT_POSITION and model.actuator_trntype[a] == sim.TRN_JOINT:
             c0[a] = model.qpos0[model.jnt_qposadr[j]]
         if model.actuator_ctrllimited[a]:
             lo, hi = model.actuator_ctrlrange[a]
