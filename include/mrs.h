@@ -464,9 +464,21 @@ int mrs_debug_phase_cycles(double* out, int n, int reset);
  * are selected), [18] the fused 16-lane solves (1: one reciprocal per lane and solve, qacc_smooth solved
  * with the friction-loss rows; 0: not a 16-lane PGS batch without helper waves, or MRS_NO_SOLVE_FUSE=1 --
  * that switch gives the same bits by the separate solves, run out of line: a reference for results, not
- * for speed).
+ * for speed), [19] the collision pairs the step walks and [20] the statically admissible pairs left out
+ * of them because their geoms can never touch (mrs_debug_pairs).
  * Returns the number of values written. */
 int mrs_debug_batch_layout(const mrs_batch* b, int* out, int n);
+/* diagnostics: the collision pairs a batch of this model walks each step, in contact order: the explicit
+ * <contact><pair>s, then the pairs the static filters admit (mrs_model_view pair_geom1/2) without those
+ * whose geoms can never touch -- each geom's centre stays in a ball fixed in the world (its own position
+ * when its body is welded to the world; about the first joint's anchor when only hinge and ball joints,
+ * one per body, lie above it), and the balls, the bounding spheres and the margin leave a gap.  Geoms below
+ * a slide or free joint or a mocap body have no such ball and keep their pairs; explicit pairs always
+ * stay.  MRS_NO_PAIR_PRUNE=1 (read here and at batch creation) keeps every pair.  Up to `max` pairs are
+ * written to geom [max][2] (may be NULL when max == 0) and the number of pruned pairs to *pruned (may be
+ * NULL); returns the count of walked pairs, which may exceed `max`, MRS_ERR_INVALID for a null or bad
+ * argument, MRS_ERR_UNSUPPORTED for a model mrs_batch_create refuses with it.  No device needed. */
+int mrs_debug_pairs(const mrs_model* m, int* geom, int max, int* pruned);
 /* diagnostics: values [0] to [15] above as mrs_batch_create would choose them for n_envs environments on
  * a device with cu_count compute units (<= 0: unknown, as when the query fails) and max_contacts (<= 0:
  * from the model), without a device: the environment switches are read, the model's tables built and

@@ -591,6 +591,16 @@ int mrs_debug_plan_layout(const mrs_model* m, int n_envs, int cu_count, int max_
   return rc == MRS_OK ? k : rc;
 }
 
+int mrs_debug_pairs(const mrs_model* m, int* geom, int max, int* pruned) {
+  int k = 0;
+  const int rc = guarded([&] {
+    if (!m) throw std::invalid_argument("null model");
+    if (max < 0 || (max > 0 && !geom)) throw std::invalid_argument("null output or negative capacity");
+    k = mrs::walked_pairs(m->m, geom, max, pruned);
+  });
+  return rc == MRS_OK ? k : rc;
+}
+
 int mrs_debug_render_plan(const mrs_model* m, int cam, int n_frames, int max_lds, long long* out, int n) {
   int k = 0;
   const int rc = guarded([&] {

@@ -18,6 +18,9 @@ int batch_num_envs(const BatchImpl* b);
 int batch_layout(const BatchImpl* b, int* out, int n);  // diagnostics: kernel configuration
 // its first 16 values as a batch of n_envs on a device with cu_count CUs would have them (no device)
 int plan_layout(const Model& m, int n_envs, int cu_count, int max_contacts, int* out, int n);
+// the collision pairs a batch of the model walks, [k][2] geom ids in contact order (up to max written;
+// returns k), and how many admissible pairs were pruned from them (no device)
+int walked_pairs(const Model& m, int* geom, int max, int* pruned);
 void batch_set_stream(BatchImpl* b, void* stream);
 void batch_reset(BatchImpl* b, int key, int env0, int n);
 // start-state pool (count rows; qvel may be null: zeros; count 0 frees it) and the masked reset

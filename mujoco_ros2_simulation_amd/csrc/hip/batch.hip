@@ -222,6 +222,7 @@ void build_devmodel(BatchImpl& b, int max_con_req, const Overrides& o) {
   b.dm.rf_static = b.dm.rf_mode ? static_cast<float*>(dalloc(b, std::max(1, b.dm.nrf) * sizeof(float))) : nullptr;
   b.group = p.group; b.g16_one_wg = p.g16_one_wg; b.wpb16 = p.wpb16; b.helpers = p.helpers; b.ext = p.ext;
   b.pair_g1 = T.pair_g1; b.pair_g2 = T.pair_g2; b.pair_dim = T.pair_dim; b.pair_mu = T.pair_mu;
+  b.pairs_pruned = T.pairs_pruned;
   b.d_dm = static_cast<DevModel*>(dalloc(b, sizeof(DevModel)));
   HIP_CHECK(hipMemcpyAsync(b.d_dm, &b.dm, sizeof(DevModel), hipMemcpyHostToDevice, b.stream));
   HIP_CHECK(hipStreamSynchronize(b.stream));  // (the host blocks of T are read until here)
@@ -505,13 +506,24 @@ void batch_free(BatchImpl* b) {
 int batch_num_envs(const BatchImpl* b) { return b->n; }
 
 int batch_layout(const BatchImpl* b, int* out, int n) {
-  int v[19];
+  int v[21];
   plan_layout_values(b->dm, b->group, b->g16_one_wg, b->wpb16, b->helpers, v);  // (the first 16: plan.h)
   v[16] = b->dm.cfrc_contact ? 1 : 0;
   v[17] = b->dm.dyn_mask;
   v[18] = b->dm.solve_fuse;
+  v[19] = b->dm.npair;
+  v[20] = b->pairs_pruned;
   int k = 0;
-  for (; k < n && k < 19; ++k) out[k] = v[k];
+  for (; k < n && k < 21; ++k) out[k] = v[k];
+  return k;
+}
+
+// mrs_debug_pairs: the pairs a batch of this model walks, as build_tables chooses them; touches no device
+int walked_pairs(const Model& m, int* geom, int max, int* pruned) {
+  const DevTables T = build_tables(m, 0, read_overrides());
+  const int k = static_cast<int>(T.pair_g1.size());
+  for (int q = 0; q < k && q < max; ++q) { geom[2 * q] = T.pair_g1[q]; geom[2 * q + 1] = T.pair_g2[q]; }
+  if (pruned) *pruned = T.pairs_pruned;
   return k;
 }
 

@@ -67,7 +67,8 @@ struct BatchImpl {
   // launch), so step launches are timed only on request
   int timing = 2;
   std::vector<float> staging;
-  std::vector<int> pair_g1, pair_g2;  // host copy of the static collision pairs (contact export)
+  std::vector<int> pair_g1, pair_g2;  // host copy of the collision pairs the device walks (contact export)
+  int pairs_pruned = 0;               // admissible pairs left out of them (devtables.h prune_pairs)
   std::vector<int> pair_dim;          // their condim and sliding friction (batch_get_contact_forces)
   std::vector<float> pair_mu;
   int dyn_asked = 0;  // the dynamics outputs asked for so far (1 << MRS_DYNOUT_*; ensure_dyn, batch_set_jac_sites)

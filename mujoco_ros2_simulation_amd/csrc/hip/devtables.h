@@ -40,6 +40,7 @@ struct Overrides {
   // than it ran before the fused form existed
   bool no_solve_fuse = false;
   bool no_ray_sweep = false; // MRS_NO_RAY_SWEEP: a static planar lidar keeps the block passes
+  bool no_pair_prune = false;  // MRS_NO_PAIR_PRUNE: the device walks every statically admissible pair (prune_pairs)
   bool no_static_rays = false;   // MRS_NO_STATIC_RAYS: no static ray split (rf_mode 0)
   bool no_static_frame = false;  // MRS_NO_STATIC_FRAME: ray tables stay in the body frame
   bool kin_twopass = false;  // MRS_KIN_TWOPASS: the kinematics' joint frames from a second pass
@@ -64,6 +65,7 @@ inline Overrides read_overrides() {
   o.no_fuse_ih = set("MRS_NO_FUSE_IH");
   o.no_solve_fuse = set("MRS_NO_SOLVE_FUSE");
   o.no_ray_sweep = set("MRS_NO_RAY_SWEEP");
+  o.no_pair_prune = set("MRS_NO_PAIR_PRUNE");
   o.no_static_rays = set("MRS_NO_STATIC_RAYS");
   o.no_static_frame = set("MRS_NO_STATIC_FRAME");
   o.kin_twopass = set("MRS_KIN_TWOPASS");
@@ -98,10 +100,14 @@ struct DevTables {
   std::vector<int> i;
   std::vector<Slot<float>> fslot;
   std::vector<Slot<int>> islot;
-  // host copies the batch keeps: the static collision pairs (contact export), their condim and sliding
-  // friction (contact forces)
+  // host copies the batch keeps: the collision pairs the device walks (contact export: a contact record
+  // holds an index into this list), their condim and sliding friction (contact forces)
   std::vector<int> pair_g1, pair_g2, pair_dim;
   std::vector<float> pair_mu;
+  // statically admissible pairs left out of that list because they can never touch (prune_pairs), and
+  // whether the full list has a general convex (MPR) pair: the plan reads the full list's properties
+  int pairs_pruned = 0;
+  bool convex_pairs = false;
   // what the plan reads again: rangefinder sensor ids, and whether every one sits on a body fixed in
   // the world
   std::vector<int> rf;
@@ -482,6 +488,110 @@ inline PairTables collision_pairs(const Model& m, DevModel& d) {
   }
   d.npair = static_cast<int>(p.g1.size());
   d.npair_explicit = static_cast<int>(m.expair_geom1.size());
+  return p;
+}
+
+// Reach ball of a geom: a centre fixed in the world and a radius rho such that the geom's centre lies
+// inside the ball for every qpos, in every env.
+//   - a geom of a body fixed in the world: its world position, rho = 0
+//   - a geom below hinge and ball joints only, at most one per body, above them bodies fixed in the
+//     world: the centre is the first joint's anchor a_1, and rho = sum |a_i - a_(i-1)| + |x_g - a_k|.
+//     A rotation about an anchor keeps every distance from it, so each term is the same at every qpos
+//     and is measured here at the pose with every joint at its reference (body_world); a jointless body
+//     in the chain only adds its fixed offset
+//   - anything else has no bound: a slide or free joint above, a mocap body above, two joints on a body
+struct Reach {
+  bool bounded = true, fixed = true;  // fixed: no joint above (then rho = 0 and `last` is unused)
+  double c[3] = {0, 0, 0}, last[3] = {0, 0, 0}, rho = 0;  // last: the lowest anchor at the reference pose
+};
+inline std::vector<Reach> geom_reach(const Model& m) {
+  auto point = [&](int body, const double* local, double out[3]) {
+    double R[9], p[3];
+    body_world(m, body, R, p);
+    for (int i = 0; i < 3; ++i) out[i] = p[i] + R[3 * i] * local[0] + R[3 * i + 1] * local[1] + R[3 * i + 2] * local[2];
+  };
+  auto dist = [](const double a[3], const double b[3]) {
+    return std::sqrt((a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2]));
+  };
+  std::vector<Reach> body(m.nbody);
+  for (int b = 1; b < m.nbody; ++b) {  // (a parent's id is below its children's)
+    Reach r = body[m.body_parentid[b]];
+    if (m.body_mocapid[b] >= 0 || m.body_jntnum[b] > 1) r.bounded = false;
+    if (r.bounded && m.body_jntnum[b] == 1) {
+      const int j = m.body_jntadr[b];
+      if (m.jnt_type[j] != MRS_JNT_HINGE && m.jnt_type[j] != MRS_JNT_BALL) r.bounded = false;
+      else {
+        double a[3];
+        point(b, &m.jnt_pos[3 * j], a);
+        if (r.fixed) std::copy(a, a + 3, r.c);
+        else r.rho += dist(a, r.last);
+        std::copy(a, a + 3, r.last);
+        r.fixed = false;
+      }
+    }
+    body[b] = r;
+  }
+  std::vector<Reach> geom(m.ngeom);
+  for (int g = 0; g < m.ngeom; ++g) {
+    Reach r = body[m.geom_bodyid[g]];
+    if (r.bounded) {
+      double x[3];
+      point(m.geom_bodyid[g], &m.geom_pos[3 * g], x);
+      if (r.fixed) std::copy(x, x + 3, r.c);
+      else r.rho += dist(x, r.last);
+    }
+    geom[g] = r;
+  }
+  return geom;
+}
+
+// The pairs the device walks: the static filter's list without the automatic pairs whose reach balls
+// prove that the geoms stay further apart than their bounding spheres plus margin.  Such a pair fails
+// the kernel's sphere test (or, against a plane, has no contact within margin) at every step in every
+// env, so leaving it out changes no result.  The slack covers the device's fp32 poses.  Explicit
+// <contact><pair>s stay (they come first and the per-env friction indexes by npair_explicit), the kept
+// pairs keep their order (the contact order), and only the walked list shrinks: contact and row
+// capacity, the scratch layout and the plan are the full list's.  MRS_NO_PAIR_PRUNE keeps every pair.
+inline bool never_touch(const Model& m, const std::vector<Reach>& reach, int ga, int gb, double margin) {
+  const auto slack = [](double r) { return r * (1 + 1e-4) + 1e-4; };
+  const bool pa = m.geom_type[ga] == MRS_GEOM_PLANE, pb = m.geom_type[gb] == MRS_GEOM_PLANE;
+  if (pa || pb) {
+    const int pl = pa ? ga : gb, g = pa ? gb : ga;
+    if (pa && pb) return false;
+    if (!fixed_in_world(m, m.geom_bodyid[pl]) || !reach[g].bounded) return false;
+    // the whole ball in front of the plane (normal: z column of the plane's world rotation)
+    double R[9], p[3], Rg[9], n[3], o[3], q[4];
+    body_world(m, m.geom_bodyid[pl], R, p);
+    const double* gq = &m.geom_quat[4 * pl];
+    const double qn = std::sqrt(gq[0] * gq[0] + gq[1] * gq[1] + gq[2] * gq[2] + gq[3] * gq[3]);
+    for (int i = 0; i < 4; ++i) q[i] = gq[i] / qn;
+    quat_to_mat(q, Rg);
+    for (int i = 0; i < 3; ++i) {
+      n[i] = R[3 * i] * Rg[2] + R[3 * i + 1] * Rg[5] + R[3 * i + 2] * Rg[8];
+      o[i] = p[i] + R[3 * i] * m.geom_pos[3 * pl] + R[3 * i + 1] * m.geom_pos[3 * pl + 1] + R[3 * i + 2] * m.geom_pos[3 * pl + 2];
+    }
+    const double h = n[0] * (reach[g].c[0] - o[0]) + n[1] * (reach[g].c[1] - o[1]) + n[2] * (reach[g].c[2] - o[2]);
+    return h > slack(reach[g].rho + m.geom_rbound[g] + margin);
+  }
+  if (!reach[ga].bounded || !reach[gb].bounded) return false;
+  const double* a = reach[ga].c;
+  const double* b = reach[gb].c;
+  const double dc = std::sqrt((a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2]));
+  return dc > slack(reach[ga].rho + reach[gb].rho + m.geom_rbound[ga] + m.geom_rbound[gb] + margin);
+}
+inline PairTables prune_pairs(const Model& m, const PairTables& all, const Overrides& o) {
+  if (o.no_pair_prune) return all;
+  const std::vector<Reach> reach = geom_reach(m);
+  PairTables p;
+  for (size_t q = 0; q < all.g1.size(); ++q) {
+    // (the margin as the kernel holds it, fp32, is the bound's)
+    if (q >= m.expair_geom1.size() && never_touch(m, reach, all.g1[q], all.g2[q], all.margin[q])) continue;
+    p.g1.push_back(all.g1[q]); p.g2.push_back(all.g2[q]); p.dim.push_back(all.dim[q]);
+    p.margin.push_back(all.margin[q]); p.gap.push_back(all.gap[q]);
+    p.fric.insert(p.fric.end(), &all.fric[3 * q], &all.fric[3 * q] + 3);
+    p.solref.insert(p.solref.end(), &all.solref[2 * q], &all.solref[2 * q] + 2);
+    p.solimp.insert(p.solimp.end(), &all.solimp[5 * q], &all.solimp[5 * q] + 5);
+  }
   return p;
 }
 
@@ -1140,7 +1250,16 @@ inline DevTables build_tables(const Model& m, int max_con_req, const Overrides& 
   using D = DevModel;
   model_counts(m, o, d);
   const TreeLists trees = tree_lists(m, o, d);
-  const PairTables pairs = collision_pairs(m, d);
+  // every count below (contact and row capacity, pipe width) is the full list's; the device tables,
+  // DevModel::npair and the host copies are the walked list's
+  const PairTables all_pairs = collision_pairs(m, d);
+  const PairTables pairs = prune_pairs(m, all_pairs, o);
+  T.pairs_pruned = static_cast<int>(all_pairs.g1.size() - pairs.g1.size());
+  for (size_t q = 0; q < all_pairs.g1.size(); ++q) {
+    const int t1 = m.geom_type[all_pairs.g1[q]], t2 = m.geom_type[all_pairs.g2[q]];
+    auto conv = [](int t) { return t == MRS_GEOM_ELLIPSOID || t == MRS_GEOM_CYLINDER || t == MRS_GEOM_MESH; };
+    if (t1 != MRS_GEOM_PLANE && t2 != MRS_GEOM_PLANE && (conv(t1) || conv(t2))) T.convex_pairs = true;
+  }
   T.pair_g1 = pairs.g1;
   T.pair_g2 = pairs.g2;
   T.pair_dim = pairs.dim;
@@ -1151,8 +1270,9 @@ inline DevTables build_tables(const Model& m, int max_con_req, const Overrides& 
   // rows outside the blocked-mode sparse solver's kinds (equality, tendon friction / limits): the
   // dense row path runs instead
   d.xrows = d.neq + d.nten_fric + d.nten_lim;
-  const KinTrees kt = kinematic_trees(m, pairs, d);
-  const RowLists rows = row_lists(m, pairs, max_con_req, d);
+  const KinTrees kt = kinematic_trees(m, all_pairs, d);
+  const RowLists rows = row_lists(m, all_pairs, max_con_req, d);
+  d.npair = static_cast<int>(pairs.g1.size());
   const ActTables act = actuator_tables(m, d);
 
   T.addi(&D::body_parentid, m.body_parentid); T.addi(&D::body_rootid, m.body_rootid);

@@ -107,7 +107,8 @@ inline ScratchLayout scratch_layout(const Model& m, const DevModel& d, bool bloc
   S.efc_hdr = take(blocked ? 24 * ne : 0);  // step.hip kHdr
   S.efc_quad = take(blocked ? 64 : 0);
   S.efc_fd = take(m.cone == MRS_CONE_ELLIPTIC && m.solver == MRS_SOL_PGS ? 2 * ne : 0);  // (16-byte aligned)
-  S.stage = take(d.npair > 0 ? 64 * kMaxPairCon * 7 : 0);  // <= 64 lanes x 8 contacts x 7 floats
+  // <= 64 lanes x 8 contacts x 7 floats (max_con > 0: the static filter admits a pair, walked or not)
+  S.stage = take(d.max_con > 0 ? 64 * kMaxPairCon * 7 : 0);
   S.efc_n = take(1);
   S.sens = take(std::max(1, m.nsensordata));
   S.xfrc = take(1);
@@ -264,12 +265,8 @@ inline Plan choose_plan(const Model& m, const DevTables& T, int n_envs, int cu_c
   // extended step kernels (step/base.h MRS_EXT) for models with general convex (MPR) pairs -- a pair
   // that is not plane-* and has an ellipsoid, cylinder or mesh (narrowphase's analytic routines cover
   // the rest) -- or rangefinders over more than 32 ray geoms
-  p.ext = d.nrgeom > 32 && d.nrf > 0;
-  for (size_t q = 0; q < T.pair_g1.size() && !p.ext; ++q) {
-    const int t1 = m.geom_type[T.pair_g1[q]], t2 = m.geom_type[T.pair_g2[q]];
-    auto conv = [](int t) { return t == MRS_GEOM_ELLIPSOID || t == MRS_GEOM_CYLINDER || t == MRS_GEOM_MESH; };
-    if (t1 != MRS_GEOM_PLANE && t2 != MRS_GEOM_PLANE && (conv(t1) || conv(t2))) p.ext = true;
-  }
+  // (DevTables::convex_pairs: of the full pair list, so pruning never changes the kernel)
+  p.ext = (d.nrgeom > 32 && d.nrf > 0) || T.convex_pairs;
   // helper waves: with one-wave workgroups (fewer waves than SIMDs, so the helpers take SIMDs that
   // would idle) every physics wave gets a second wave that runs its envs' collision pass, builds their
   // constraint rows, traces their rangefinders and factors the integrator's M + h D each step while it

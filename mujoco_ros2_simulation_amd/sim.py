@@ -311,6 +311,8 @@ def lib() -> C.CDLL:
         L.mrs_debug_plan_layout.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         if hasattr(L, "mrs_debug_render_plan"):  # (an A/B library named by MRS_LIB may predate it)
             L.mrs_debug_render_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        if hasattr(L, "mrs_debug_pairs"):  # (likewise)
+            L.mrs_debug_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -454,6 +456,8 @@ LAYOUT_OUTPUT_KEYS = ["contact_wrench"]
 LAYOUT_DYN_KEYS = ["dyn_outputs"]
 # and last: 1 when the 16-lane solves are fused (0 otherwise, and under MRS_NO_SOLVE_FUSE=1)
 LAYOUT_SOLVE_KEYS = ["solve_fuse"]
+# then the collision pairs the step walks, and the admissible pairs pruned from them (walked_pairs)
+LAYOUT_PAIR_KEYS = ["pairs", "pairs_pruned"]
 
 
 def plan_layout(model: "Model", n_envs: int, cu_count: int, max_contacts: int = 0) -> dict:
@@ -464,6 +468,19 @@ def plan_layout(model: "Model", n_envs: int, cu_count: int, max_contacts: int = 
     if k < 0:
         raise MrsError(k, lib().mrs_last_error().decode())
     return dict(zip(LAYOUT_KEYS[:k], out[:k].tolist()))
+
+
+def walked_pairs(model: "Model") -> tuple[np.ndarray, int]:
+    """the collision pairs a batch of this model walks each step, [k][2] geom ids in contact order, and
+    the number of statically admissible pairs pruned from them because their geoms can never touch
+    (mrs_debug_pairs; MRS_NO_PAIR_PRUNE=1 keeps every pair).  Needs no GPU"""
+    pruned = C.c_int(0)
+    k = lib().mrs_debug_pairs(model.handle, None, 0, C.byref(pruned))
+    if k < 0:
+        raise MrsError(k, lib().mrs_last_error().decode())
+    out = np.zeros((k, 2), dtype=np.int32)
+    lib().mrs_debug_pairs(model.handle, out.ctypes.data if k else None, k, None)
+    return out, pruned.value
 
 
 RENDER_KERNELS = ["binned", "frame", "tile"]  # depth_kernel_mesh, depth_kernel_v2, depth_kernel
@@ -697,7 +714,7 @@ class Batch:
     def layout(self) -> dict:
         """kernel configuration of this batch (diagnostics): group width, LDS and scratch floats per
         env, blocked mode, pipe width, row and contact capacity, kinematic trees"""
-        keys = LAYOUT_KEYS + LAYOUT_OUTPUT_KEYS + LAYOUT_DYN_KEYS + LAYOUT_SOLVE_KEYS
+        keys = LAYOUT_KEYS + LAYOUT_OUTPUT_KEYS + LAYOUT_DYN_KEYS + LAYOUT_SOLVE_KEYS + LAYOUT_PAIR_KEYS
         out = np.zeros(len(keys), dtype=np.int32)
         k = lib().mrs_debug_batch_layout(self._h, out.ctypes.data, len(keys))
         return dict(zip(keys[:k], out[:k].tolist()))
