@@ -465,7 +465,9 @@ int mrs_debug_phase_cycles(double* out, int n, int reset);
  * with the friction-loss rows; 0: not a 16-lane PGS batch without helper waves, or MRS_NO_SOLVE_FUSE=1 --
  * that switch gives the same bits by the separate solves, run out of line: a reference for results, not
  * for speed), [19] the collision pairs the step walks and [20] the statically admissible pairs left out
- * of them because their geoms can never touch (mrs_debug_pairs).
+ * of them because their geoms can never touch (mrs_debug_pairs), [21] the launches stage the workgroup-
+ * shared tables from one packed image (1) or table by table, out of line (0: MRS_NO_TABLE_IMAGE=1 at batch
+ * creation, a reference for results, not for speed).
  * Returns the number of values written. */
 int mrs_debug_batch_layout(const mrs_batch* b, int* out, int n);
 /* diagnostics: the collision pairs a batch of this model walks each step, in contact order: the explicit
@@ -485,6 +487,21 @@ int mrs_debug_pairs(const mrs_model* m, int* geom, int max, int* pruned);
  * the plan chosen, nothing else.  Returns the number of values written, MRS_ERR_INVALID for a null or
  * bad argument, MRS_ERR_UNSUPPORTED for a model mrs_batch_create refuses with it. */
 int mrs_debug_plan_layout(const mrs_model* m, int n_envs, int cu_count, int max_contacts, int* out, int n);
+/* diagnostics: the workgroup-shared tables of the step kernel as the one packed image a batch uploads and
+ * every launch copies into LDS (the same arguments as mrs_debug_plan_layout choose the plan): up to `max`
+ * floats of it to image (may be NULL when max == 0), and to offsets[0..17] the plan's table offsets in
+ * floats -- ray directions, static ray hits, ray blocks, sensor records, friction-loss rows, limit rows,
+ * actuator, dof, body, mass-matrix pair, jump, kinematics body / joint / geom tables (the ray-geom records
+ * are at 0), the end of the tables, the workgroup's shared floats -- then [16] blocked mode and [17] the
+ * floats a launch copies (the tables' end; in blocked mode the actuator table's offset).  Returns the
+ * image's length, a multiple of 4 (zero-padded).  No device needed. */
+int mrs_debug_table_image(const mrs_model* m, int n_envs, int cu_count, int max_contacts, float* image, int max,
+                          int* offsets, int n_off);
+/* diagnostics: table `which` of those the image holds, as the model block holds it: 0 ray geoms, 1 rays (8
+ * floats each), 2 ray blocks, 3 sensor records, 4 friction-loss rows, 5 limit rows, 6 actuators, 7 dofs,
+ * 8 bodies, 9 mass-matrix pairs, 10 the jump table (int bits), 11 / 12 / 13 kinematics bodies / joints /
+ * geoms.  Up to `max` floats to out; returns the table's length.  No device needed. */
+int mrs_debug_staged_table(const mrs_model* m, int max_contacts, int which, float* out, int max);
 /* diagnostics: how mrs_batch_render_depth / mrs_batch_render_async would render n_frames frames of camera
  * `cam` on a device with max_lds bytes of LDS per workgroup, without a device: the render switches
  * (MRS_DEPTH_V1, MRS_DEPTH_V2, MRS_RAST_BUDGET_MB) are read and the plan chosen, nothing else.  Values: [0]

@@ -601,6 +601,29 @@ int mrs_debug_pairs(const mrs_model* m, int* geom, int max, int* pruned) {
   return rc == MRS_OK ? k : rc;
 }
 
+int mrs_debug_table_image(const mrs_model* m, int n_envs, int cu_count, int max_contacts, float* image, int max,
+                          int* offsets, int n_off) {
+  int k = 0;
+  const int rc = guarded([&] {
+    if (!m) throw std::invalid_argument("null model");
+    if (n_envs < 1) throw std::invalid_argument("n_envs must be positive");
+    if (max < 0 || (max > 0 && !image) || n_off < 0 || (n_off > 0 && !offsets))
+      throw std::invalid_argument("null output or negative capacity");
+    k = mrs::table_image(m->m, n_envs, cu_count, max_contacts, image, max, offsets, n_off);
+  });
+  return rc == MRS_OK ? k : rc;
+}
+
+int mrs_debug_staged_table(const mrs_model* m, int max_contacts, int which, float* out, int max) {
+  int k = 0;
+  const int rc = guarded([&] {
+    if (!m) throw std::invalid_argument("null model");
+    if (max < 0 || (max > 0 && !out)) throw std::invalid_argument("null output or negative capacity");
+    k = mrs::staged_table(m->m, max_contacts, which, out, max);
+  });
+  return rc == MRS_OK ? k : rc;
+}
+
 int mrs_debug_render_plan(const mrs_model* m, int cam, int n_frames, int max_lds, long long* out, int n) {
   int k = 0;
   const int rc = guarded([&] {

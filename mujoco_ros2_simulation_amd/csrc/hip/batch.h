@@ -21,6 +21,9 @@ int plan_layout(const Model& m, int n_envs, int cu_count, int max_contacts, int*
 // the collision pairs a batch of the model walks, [k][2] geom ids in contact order (up to max written;
 // returns k), and how many admissible pairs were pruned from them (no device)
 int walked_pairs(const Model& m, int* geom, int max, int* pruned);
+// the packed workgroup-shared table image of a plan and its offsets, and one staged table as packed
+int table_image(const Model& m, int n_envs, int cu_count, int max_contacts, float* image, int max, int* offsets, int n_off);
+int staged_table(const Model& m, int max_contacts, int which, float* out, int max);
 void batch_set_stream(BatchImpl* b, void* stream);
 void batch_reset(BatchImpl* b, int key, int env0, int n);
 // start-state pool (count rows; qvel may be null: zeros; count 0 frees it) and the masked reset

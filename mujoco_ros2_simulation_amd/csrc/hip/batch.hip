@@ -219,7 +219,20 @@ void build_devmodel(BatchImpl& b, int max_con_req, const Overrides& o) {
   HIP_CHECK(hipMemcpyAsync(b.dblock_f, T.f.data(), T.f.size() * sizeof(float), hipMemcpyHostToDevice, b.stream));
   HIP_CHECK(hipMemcpyAsync(b.dblock_i, T.i.data(), T.i.size() * sizeof(int), hipMemcpyHostToDevice, b.stream));
   T.patch(b.dm, static_cast<const float*>(b.dblock_f), static_cast<const int*>(b.dblock_i));
-  b.dm.rf_static = b.dm.rf_mode ? static_cast<float*>(dalloc(b, std::max(1, b.dm.nrf) * sizeof(float))) : nullptr;
+  // the workgroup-shared tables as one image (DevModel::shr_image), which the launches copy; the static
+  // ray hits live inside it, where the producer pass writes them.  No later call writes a staged table
+  // (set_param / set_inertial fill per-env rows), so the image stays what it is here
+  const std::vector<float> image = o.no_table_image ? std::vector<float>() : pack_shared_image(T, b.dm);
+  float* d_image = nullptr;
+  if (!o.no_table_image) {
+    d_image = static_cast<float*>(dalloc(b, image.size() * sizeof(float)));
+    if (!image.empty())
+      HIP_CHECK(hipMemcpyAsync(d_image, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice, b.stream));
+    b.dm.shr_image = d_image;
+  }
+  b.dm.rf_static = !b.dm.rf_mode ? nullptr
+                   : d_image     ? d_image + b.dm.shr_rfst
+                                 : static_cast<float*>(dalloc(b, std::max(1, b.dm.nrf) * sizeof(float)));
   b.group = p.group; b.g16_one_wg = p.g16_one_wg; b.wpb16 = p.wpb16; b.helpers = p.helpers; b.ext = p.ext;
   b.pair_g1 = T.pair_g1; b.pair_g2 = T.pair_g2; b.pair_dim = T.pair_dim; b.pair_mu = T.pair_mu;
   b.pairs_pruned = T.pairs_pruned;
@@ -506,15 +519,16 @@ void batch_free(BatchImpl* b) {
 int batch_num_envs(const BatchImpl* b) { return b->n; }
 
 int batch_layout(const BatchImpl* b, int* out, int n) {
-  int v[21];
+  int v[22];
   plan_layout_values(b->dm, b->group, b->g16_one_wg, b->wpb16, b->helpers, v);  // (the first 16: plan.h)
   v[16] = b->dm.cfrc_contact ? 1 : 0;
   v[17] = b->dm.dyn_mask;
   v[18] = b->dm.solve_fuse;
   v[19] = b->dm.npair;
   v[20] = b->pairs_pruned;
+  v[21] = b->dm.shr_image.p ? 1 : 0;
   int k = 0;
-  for (; k < n && k < 21; ++k) out[k] = v[k];
+  for (; k < n && k < 22; ++k) out[k] = v[k];
   return k;
 }
 
@@ -525,6 +539,45 @@ int walked_pairs(const Model& m, int* geom, int max, int* pruned) {
   for (int q = 0; q < k && q < max; ++q) { geom[2 * q] = T.pair_g1[q]; geom[2 * q + 1] = T.pair_g2[q]; }
   if (pruned) *pruned = T.pairs_pruned;
   return k;
+}
+
+// mrs_debug_table_image: the packed image of the workgroup-shared tables as a batch of this plan would
+// upload it, and the plan's shr_* offsets; touches no device
+int table_image(const Model& m, int n_envs, int cu_count, int max_contacts, float* image, int max, int* offsets, int n_off) {
+  const Overrides o = read_overrides();
+  const DevTables T = build_tables(m, max_contacts, o);
+  const Plan p = choose_plan(m, T, n_envs, cu_count, o);
+  const DevModel& d = p.dm;
+  const std::vector<float> img = pack_shared_image(T, d);
+  for (int k = 0; k < max && k < static_cast<int>(img.size()); ++k) image[k] = img[k];
+  const int off[18] = {d.shr_rf, d.shr_rfst, d.shr_blk, d.shr_sens, d.shr_fric, d.shr_lim, d.shr_act, d.shr_dof, d.shr_body,
+                       d.shr_mpair, d.shr_jump, d.shr_kbody, d.shr_kjnt, d.shr_kgeom, d.shr_flag, d.shr_total, d.blocked,
+                       shared_image_floats(d)};
+  for (int k = 0; k < n_off && k < 18; ++k) offsets[k] = off[k];
+  return static_cast<int>(img.size());
+}
+
+// mrs_debug_staged_table: one of the tables the launches stage, as build_tables packs it (jump: int bits)
+int staged_table(const Model& m, int max_contacts, int which, float* out, int max) {
+  using D = DevModel;
+  const DevTables T = build_tables(m, max_contacts, read_overrides());
+  CPtr<float> D::*const ftab[14] = {&D::rgeom, &D::rfray, &D::rfblk, &D::sensrec, &D::fricrec, &D::limrec, &D::actrec,
+                                    &D::dofrec, &D::bodytab, &D::mpairtab, nullptr, &D::kinbody, &D::kinjnt, &D::kingeom};
+  if (which < 0 || which >= 14) throw std::invalid_argument("unknown staged table");
+  if (!ftab[which]) {
+    for (const auto& s : T.islot)
+      if (s.member == &D::jump) {
+        for (size_t k = 0; k < s.len && static_cast<int>(k) < max; ++k) out[k] = int_bits(T.i[s.off + k]);
+        return static_cast<int>(s.len);
+      }
+    throw std::logic_error("table not packed");
+  }
+  for (const auto& s : T.fslot)
+    if (s.member == ftab[which]) {
+      for (size_t k = 0; k < s.len && static_cast<int>(k) < max; ++k) out[k] = T.f[s.off + k];
+      return static_cast<int>(s.len);
+    }
+  throw std::logic_error("table not packed");
 }
 
 // mrs_debug_plan_layout: the overrides, the tables and the plan of a model; touches no device

@@ -322,6 +322,15 @@ struct DevModel {
   // their offsets
   int nact_site, nact_site_vel;
   CPtr<float> sact;
+  // the workgroup-shared tables as one packed image (devtables.h pack_shared_image): the
+  // floats a launch stages at shr_off, table by table at their shr_* offsets and in the staged form (rfray's
+  // 4 of 8 floats per ray, jump as int bits), up to shr_flag (blocked mode: shr_act), zero-padded to a
+  // multiple of 4 and 16-byte aligned, so step_kernel copies it with 16-byte loads issued back to back.
+  // rf_static points into it at shr_rfst: the static ray split writes its hits in place.  Constant from
+  // batch creation on (no later call writes a staged table).  Null (MRS_NO_TABLE_IMAGE=1, a reference for
+  // the bits): the launch stages table by table, out of line.  Kept last: the fields above keep their
+  // offsets
+  CPtr<float> shr_image;
 };
 constexpr int kRayBlock = 128;
 // bits of DevModel::prm_mask (1 << MRS_PARAM_*)

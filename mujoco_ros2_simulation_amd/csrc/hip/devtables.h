@@ -39,6 +39,9 @@ struct Overrides {
   // bit-identity reference only, not a speed baseline: the separate form then runs out of line, slower
   // than it ran before the fused form existed
   bool no_solve_fuse = false;
+  // MRS_NO_TABLE_IMAGE: the launch stages the workgroup-shared tables one by one (DevModel::shr_image
+  // null).  A bit-identity reference only, like MRS_NO_SOLVE_FUSE: that form runs out of line
+  bool no_table_image = false;
   bool no_ray_sweep = false; // MRS_NO_RAY_SWEEP: a static planar lidar keeps the block passes
   bool no_pair_prune = false;  // MRS_NO_PAIR_PRUNE: the device walks every statically admissible pair (prune_pairs)
   bool no_static_rays = false;   // MRS_NO_STATIC_RAYS: no static ray split (rf_mode 0)
@@ -64,6 +67,7 @@ inline Overrides read_overrides() {
   o.ray_helpers = num("MRS_RAY_HELPERS", 1) != 0;
   o.no_fuse_ih = set("MRS_NO_FUSE_IH");
   o.no_solve_fuse = set("MRS_NO_SOLVE_FUSE");
+  o.no_table_image = set("MRS_NO_TABLE_IMAGE");
   o.no_ray_sweep = set("MRS_NO_RAY_SWEEP");
   o.no_pair_prune = set("MRS_NO_PAIR_PRUNE");
   o.no_static_rays = set("MRS_NO_STATIC_RAYS");
@@ -132,6 +136,12 @@ struct DevTables {
   const float* table(CPtr<float> DevModel::*member) const {
     for (const auto& s : fslot)
       if (s.member == member) return f.data() + s.off;
+    throw std::logic_error("table not packed");
+  }
+  // a packed int32 table on the host
+  const int* itable(CPtr<int> DevModel::*member) const {
+    for (const auto& s : islot)
+      if (s.member == member) return i.data() + s.off;
     throw std::logic_error("table not packed");
   }
   // the tables' addresses once the blocks live at fbase / ibase
@@ -1375,6 +1385,46 @@ inline DevTables build_tables(const Model& m, int max_con_req, const Overrides& 
   // site actuators, likewise after every table a model without one has
   if (d.nact_site > 0) T.addf(&D::sact, act.site);
   return T;
+}
+
+// ------------------------------------------------------------------ the shared tables as one image
+// floats of the image a launch copies: the staged tables end at shr_flag (the helper waves' signal words
+// after them are the kernel's own), in blocked mode at shr_act
+inline int shared_image_floats(const DevModel& d) { return d.blocked ? d.shr_act : d.shr_flag; }
+
+// The workgroup-shared tables of plan d (its shr_* offsets, plan.h shared_layout) packed as the launch
+// stages them (DevModel::shr_image): each table at its offset, as long as the gap to the next one --
+// rfray as floats 0..3 of each ray's 8 (direction, sensordata address; none without rf_common), jump as
+// int bits, the static ray hits' extent zero (the producer pass writes it on the device).  Zero-padded
+// to a multiple of 4 floats
+inline std::vector<float> pack_shared_image(const DevTables& T, const DevModel& d) {
+  using D = DevModel;
+  const int n = shared_image_floats(d);
+  std::vector<float> img(static_cast<size_t>((n + 3) & ~3), 0.0f);
+  // (a blocked plan's tables end at shr_act: the extents from there on are outside the image)
+  auto put = [&](int off, int end, const float* src) {
+    for (int k = off; k < end && k < n; ++k) img[k] = src[k - off];
+  };
+  put(0, d.shr_rf, T.table(&D::rgeom));
+  const float* rfray = T.table(&D::rfray);
+  for (int k = d.shr_rf; k < d.shr_rfst; ++k) {
+    const int q = k - d.shr_rf;
+    img[k] = rfray[8 * (q >> 2) + (q & 3)];
+  }
+  put(d.shr_blk, d.shr_sens, T.table(&D::rfblk));
+  put(d.shr_sens, d.shr_fric, T.table(&D::sensrec));
+  put(d.shr_fric, d.shr_lim, T.table(&D::fricrec));
+  put(d.shr_lim, d.shr_act, T.table(&D::limrec));
+  put(d.shr_act, d.shr_dof, T.table(&D::actrec));
+  put(d.shr_dof, d.shr_body, T.table(&D::dofrec));
+  put(d.shr_body, d.shr_mpair, T.table(&D::bodytab));
+  put(d.shr_mpair, d.shr_jump, T.table(&D::mpairtab));
+  const int* jump = T.itable(&D::jump);
+  for (int k = d.shr_jump; k < d.shr_kbody && k < n; ++k) img[k] = int_bits(jump[k - d.shr_jump]);
+  put(d.shr_kbody, d.shr_kjnt, T.table(&D::kinbody));
+  put(d.shr_kjnt, d.shr_kgeom, T.table(&D::kinjnt));
+  put(d.shr_kgeom, d.shr_flag, T.table(&D::kingeom));
+  return img;
 }
 
 }  // namespace mrs

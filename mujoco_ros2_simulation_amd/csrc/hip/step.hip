@@ -8062,6 +8062,78 @@ __device__ void rk4_final(ENV_PARAMS) {
   integrate_pos<G>(m, s, sv, h, lane);
 }
 
+// The workgroup-shared tables (DevModel::shr_*) staged table by table: the form the launches had before the
+// packed image, kept as its reference for the bits (DevModel::shr_image null, MRS_NO_TABLE_IMAGE=1) and
+// called out of line, so the kernels hold the image copy only
+template <int G>
+__device__ void stage_tables(const DevModel& m, float* shr) {
+  #pragma unroll 1
+  for (int i = threadIdx.x; i < m.shr_rf; i += blockDim.x) shr[i] = m.rgeom[i];
+  #pragma unroll 1
+  for (int i = threadIdx.x; i < m.shr_rfst - m.shr_rf; i += blockDim.x) shr[m.shr_rf + i] = m.rfray[8 * (i >> 2) + (i & 3)];
+  if (m.rf_mode == 2)
+    #pragma unroll 1
+    for (int i = threadIdx.x; i < m.nrf; i += blockDim.x) shr[m.shr_rfst + i] = m.rf_static[i];
+  #pragma unroll 1
+  for (int i = threadIdx.x; i < 17 * m.nrfblk; i += blockDim.x) shr[m.shr_blk + i] = m.rfblk[i];
+  #pragma unroll 1
+  for (int i = threadIdx.x; i < m.shr_fric - m.shr_sens; i += blockDim.x) shr[m.shr_sens + i] = m.sensrec[i];
+  #pragma unroll 1
+  for (int i = threadIdx.x; i < 4 * m.nfric; i += blockDim.x) shr[m.shr_fric + i] = m.fricrec[i];
+  #pragma unroll 1
+  for (int i = threadIdx.x; i < 4 * m.nlim; i += blockDim.x) shr[m.shr_lim + i] = m.limrec[i];
+  if constexpr (G < 64) {  // smooth-dynamics tables (blocked mode reads the model block)
+    #pragma unroll 1
+    for (int i = threadIdx.x; i < 20 * m.nu; i += blockDim.x) shr[m.shr_act + i] = m.actrec[i];
+    #pragma unroll 1
+    for (int i = threadIdx.x; i < 16 * m.nv; i += blockDim.x) shr[m.shr_dof + i] = m.dofrec[i];
+    #pragma unroll 1
+    for (int i = threadIdx.x; i < 8 * m.nbody; i += blockDim.x) shr[m.shr_body + i] = m.bodytab[i];
+    #pragma unroll 1
+    for (int i = threadIdx.x; i < 4 * m.nMpair; i += blockDim.x) shr[m.shr_mpair + i] = m.mpairtab[i];
+    #pragma unroll 1
+    for (int i = threadIdx.x; i < m.njump * m.nbody; i += blockDim.x) shr[m.shr_jump + i] = __int_as_float(m.jump[i]);
+    #pragma unroll 1
+    for (int i = threadIdx.x; i < 25 * m.nbody; i += blockDim.x) shr[m.shr_kbody + i] = m.kinbody[i];
+    #pragma unroll 1
+    for (int i = threadIdx.x; i < 13 * m.njnt; i += blockDim.x) shr[m.shr_kjnt + i] = m.kinjnt[i];
+    #pragma unroll 1
+    for (int i = threadIdx.x; i < 9 * m.ngeom; i += blockDim.x) shr[m.shr_kgeom + i] = m.kingeom[i];
+  }
+}
+
+// The same tables from the packed image (DevModel::shr_image: n floats, zero-padded to a multiple of 4, 16
+// bytes aligned like shr): every thread loads up to kImageDepth 16-byte vectors back to back, then stores
+// them -- one wait for the batch where the tables took a round trip each.  A larger image takes further
+// batches.  The last vector of an n that is no multiple of 4 is stored by the word: the LDS extent ends at n
+#ifndef MRS_IMAGE_DEPTH
+#define MRS_IMAGE_DEPTH 4
+#endif
+constexpr int kImageDepth = MRS_IMAGE_DEPTH;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void stage_table_image(const DevModel& m, float* shr, int n) {
+  const __attribute__((address_space(4))) f32x4* img = (const __attribute__((address_space(4))) f32x4*)m.shr_image.p;
+  const int nvec = (n + 3) >> 2, stride = blockDim.x;
+  #pragma unroll 1
+  for (int base = threadIdx.x; base < nvec; base += kImageDepth * stride) {
+    f32x4 v[kImageDepth];
+    // (a vector past the end re-reads the last one and is not stored: the loads stay unconditional)
+    #pragma unroll
+    for (int k = 0; k < kImageDepth; ++k) v[k] = img[min(base + k * stride, nvec - 1)];
+    #pragma unroll
+    for (int k = 0; k < kImageDepth; ++k) {
+      const int i = base + k * stride;
+      if (4 * i + 4 <= n) {
+        *(f32x4*)(shr + 4 * i) = v[k];
+      } else if (i < nvec) {
+        const float w[4] = {v[k].x, v[k].y, v[k].z, v[k].w};
+        for (int c = 0; c < 4; ++c)
+          if (4 * i + c < n) shr[4 * i + c] = w[c];
+      }
+    }
+  }
+}
+
 // waves per SIMD the register budget is sized for.  One env per wave (G = 64, blocked mode): 2 waves
 // (256 VGPRs) -- the register-resident sparse PGS holds up to 64 rows per pipe, and the per-env LDS of
 // the multi-tree scenes that pick G = 64 (C5: ~13 KB) allows ~2 waves per SIMD anyway.  With G < 64
@@ -8111,19 +8183,48 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
   lfloat* s = (lfloat*)(smem + slot * L.total);
   gfloat* scr = (gfloat*)(st.scratch + (size_t)(valid || st.spread_shift == 0 ? env : st.scr_mirror + vgroup) * m.S.total);
   const size_t e = (size_t)(env < n_envs ? env : n_envs - 1);
+  // The launch's loads as one batch: the env's state (each lane its first element of every array, and the
+  // time) is loaded here, the table image after it, and the LDS stores follow both, so the loads are in
+  // flight together instead of one round trip after another
+  const int nq_l = is_helper ? 0 : m.nq, nv_l = is_helper ? 0 : m.nv, nu_l = is_helper ? 0 : m.nu, na_l = is_helper ? 0 : m.na;
+  float q0 = 0, v0 = 0, fa0 = 0, ws0 = 0, c0 = 0, a0 = 0;
+  if (lane < nq_l) q0 = st.qpos[e * m.nq + lane];
+  if (lane < nv_l) {
+    v0 = st.qvel[e * m.nv + lane];
+    fa0 = st.qfrc_applied[e * m.nv + lane];
+    ws0 = st.qacc_ws[e * m.nv + lane];
+  }
+  if (lane < nu_l) c0 = st.ctrl[e * m.nu + lane];
+  if (lane < na_l) a0 = st.act[e * m.na + lane];
+  double time = st.time[e];
+  // workgroup-shared tables (DevModel::shr_*)
+  if (m.shr_image.p) stage_table_image(m, smem + m.shr_off, G == 64 ? m.shr_act : m.shr_flag);
+  else { [[clang::noinline]] stage_tables<G>(m, smem + m.shr_off); }
+  if (lane < nq_l) s[L.qpos + lane] = q0;
+  if (lane < nv_l) {
+    s[L.qvel + lane] = v0;
+    s[L.qfrc_applied + lane] = fa0;
+    s[L.qacc_ws + lane] = ws0;
+  }
+  if (lane < nu_l) s[L.ctrl + lane] = c0;
+  // the activations, and act_dot zero until a forward pass writes it (MRS_DSBL_ACTUATION: never)
+  if (lane < na_l) {
+    s[L.act + lane] = a0;
+    s[L.act + m.na + lane] = 0;
+  }
+  // (arrays longer than the lane group: the rest of them)
   #pragma unroll 1
-  for (int i = lane; i < (is_helper ? 0 : m.nq); i += G) s[L.qpos + i] = st.qpos[e * m.nq + i];
+  for (int i = lane + G; i < nq_l; i += G) s[L.qpos + i] = st.qpos[e * m.nq + i];
   #pragma unroll 1
-  for (int i = lane; i < (is_helper ? 0 : m.nv); i += G) {
+  for (int i = lane + G; i < nv_l; i += G) {
     s[L.qvel + i] = st.qvel[e * m.nv + i];
     s[L.qfrc_applied + i] = st.qfrc_applied[e * m.nv + i];
     s[L.qacc_ws + i] = st.qacc_ws[e * m.nv + i];
   }
   #pragma unroll 1
-  for (int i = lane; i < (is_helper ? 0 : m.nu); i += G) s[L.ctrl + i] = st.ctrl[e * m.nu + i];
-  // the activations, and act_dot zero until a forward pass writes it (MRS_DSBL_ACTUATION: never)
+  for (int i = lane + G; i < nu_l; i += G) s[L.ctrl + i] = st.ctrl[e * m.nu + i];
   #pragma unroll 1
-  for (int i = lane; i < (is_helper ? 0 : m.na); i += G) {
+  for (int i = lane + G; i < na_l; i += G) {
     s[L.act + i] = st.act[e * m.na + i];
     s[L.act + m.na + i] = 0;
   }
@@ -8154,45 +8255,7 @@ __global__ __launch_bounds__(64 * WavesPerBlock<G>::value, kHelpers ? MRS_HELPER
       s[L.dofb + 2 * j + 1] = __int_as_float(m.body_subtree_end[bj]);
     }
   }
-  double time = st.time[e];
   gfloat* sensordata = valid ? (gfloat*)(st.sensordata + e * m.nsensordata) : scr + m.S.sens;
-  {
-    // workgroup-shared tables (DevModel::shr_*): ray-geom records and per-ray direction + address
-    float* shr = smem + m.shr_off;
-    #pragma unroll 1
-    for (int i = threadIdx.x; i < m.shr_rf; i += blockDim.x) shr[i] = m.rgeom[i];
-    #pragma unroll 1
-    for (int i = threadIdx.x; i < m.shr_rfst - m.shr_rf; i += blockDim.x) shr[m.shr_rf + i] = m.rfray[8 * (i >> 2) + (i & 3)];
-    if (m.rf_mode == 2)
-      #pragma unroll 1
-      for (int i = threadIdx.x; i < m.nrf; i += blockDim.x) shr[m.shr_rfst + i] = m.rf_static[i];
-    #pragma unroll 1
-    for (int i = threadIdx.x; i < 17 * m.nrfblk; i += blockDim.x) shr[m.shr_blk + i] = m.rfblk[i];
-    #pragma unroll 1
-    for (int i = threadIdx.x; i < m.shr_fric - m.shr_sens; i += blockDim.x) shr[m.shr_sens + i] = m.sensrec[i];
-    #pragma unroll 1
-    for (int i = threadIdx.x; i < 4 * m.nfric; i += blockDim.x) shr[m.shr_fric + i] = m.fricrec[i];
-    #pragma unroll 1
-    for (int i = threadIdx.x; i < 4 * m.nlim; i += blockDim.x) shr[m.shr_lim + i] = m.limrec[i];
-    if constexpr (G < 64) {  // smooth-dynamics tables (blocked mode reads the model block)
-      #pragma unroll 1
-      for (int i = threadIdx.x; i < 20 * m.nu; i += blockDim.x) shr[m.shr_act + i] = m.actrec[i];
-      #pragma unroll 1
-      for (int i = threadIdx.x; i < 16 * m.nv; i += blockDim.x) shr[m.shr_dof + i] = m.dofrec[i];
-      #pragma unroll 1
-      for (int i = threadIdx.x; i < 8 * m.nbody; i += blockDim.x) shr[m.shr_body + i] = m.bodytab[i];
-      #pragma unroll 1
-      for (int i = threadIdx.x; i < 4 * m.nMpair; i += blockDim.x) shr[m.shr_mpair + i] = m.mpairtab[i];
-      #pragma unroll 1
-      for (int i = threadIdx.x; i < m.njump * m.nbody; i += blockDim.x) shr[m.shr_jump + i] = __int_as_float(m.jump[i]);
-      #pragma unroll 1
-      for (int i = threadIdx.x; i < 25 * m.nbody; i += blockDim.x) shr[m.shr_kbody + i] = m.kinbody[i];
-      #pragma unroll 1
-      for (int i = threadIdx.x; i < 13 * m.njnt; i += blockDim.x) shr[m.shr_kjnt + i] = m.kinjnt[i];
-      #pragma unroll 1
-      for (int i = threadIdx.x; i < 9 * m.ngeom; i += blockDim.x) shr[m.shr_kgeom + i] = m.kingeom[i];
-    }
-  }
   if (helpers && threadIdx.x < 4) *helper_flag(m, threadIdx.x) = 0;
   __syncthreads();
   wsync();

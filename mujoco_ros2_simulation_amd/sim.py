@@ -313,6 +313,9 @@ def lib() -> C.CDLL:
             L.mrs_debug_render_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         if hasattr(L, "mrs_debug_pairs"):  # (likewise)
             L.mrs_debug_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        if hasattr(L, "mrs_debug_table_image"):  # (likewise)
+            L.mrs_debug_table_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+            L.mrs_debug_staged_table.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -458,6 +461,9 @@ LAYOUT_DYN_KEYS = ["dyn_outputs"]
 LAYOUT_SOLVE_KEYS = ["solve_fuse"]
 # then the collision pairs the step walks, and the admissible pairs pruned from them (walked_pairs)
 LAYOUT_PAIR_KEYS = ["pairs", "pairs_pruned"]
+# and: 1 when the launches stage the workgroup-shared tables from one packed image (0 under
+# MRS_NO_TABLE_IMAGE=1: table by table)
+LAYOUT_IMAGE_KEYS = ["table_image"]
 
 
 def plan_layout(model: "Model", n_envs: int, cu_count: int, max_contacts: int = 0) -> dict:
@@ -481,6 +487,39 @@ def walked_pairs(model: "Model") -> tuple[np.ndarray, int]:
     out = np.zeros((k, 2), dtype=np.int32)
     lib().mrs_debug_pairs(model.handle, out.ctypes.data if k else None, k, None)
     return out, pruned.value
+
+
+# the tables of the packed image in offset order (table_image), and their ids for staged_table
+IMAGE_TABLES = ["rgeom", "rfray", "rf_static", "rfblk", "sensrec", "fricrec", "limrec", "actrec", "dofrec", "bodytab",
+                "mpairtab", "jump", "kinbody", "kinjnt", "kingeom"]
+STAGED_TABLE_IDS = {name: k for k, name in enumerate(t for t in IMAGE_TABLES if t != "rf_static")}
+
+
+def table_image(model: "Model", n_envs: int, cu_count: int, max_contacts: int = 0) -> dict:
+    """the packed image of the step kernel's workgroup-shared tables as a batch of this plan uploads it
+    (mrs_debug_table_image): "image" (fp32, zero-padded to a multiple of 4), "offsets" (table name -> first
+    float, in IMAGE_TABLES order, plus "end" and "shared_floats"), "blocked" and "copied" (the floats a
+    launch copies).  Needs no GPU"""
+    off = np.zeros(18, dtype=np.int32)
+    k = lib().mrs_debug_table_image(model.handle, n_envs, cu_count, max_contacts, None, 0, off.ctypes.data, len(off))
+    if k < 0:
+        raise MrsError(k, lib().mrs_last_error().decode())
+    img = np.zeros(k, dtype=np.float32)
+    lib().mrs_debug_table_image(model.handle, n_envs, cu_count, max_contacts, img.ctypes.data if k else None, k, None, 0)
+    offsets = dict(zip(IMAGE_TABLES + ["end", "shared_floats"], [0] + off[:16].tolist()))
+    return {"image": img, "offsets": offsets, "blocked": int(off[16]), "copied": int(off[17])}
+
+
+def staged_table(model: "Model", name: str, max_contacts: int = 0) -> np.ndarray:
+    """one of the tables the image holds, as the model block holds it (mrs_debug_staged_table): fp32; the
+    jump table's ints as bits.  Needs no GPU"""
+    which = STAGED_TABLE_IDS[name]
+    k = lib().mrs_debug_staged_table(model.handle, max_contacts, which, None, 0)
+    if k < 0:
+        raise MrsError(k, lib().mrs_last_error().decode())
+    out = np.zeros(k, dtype=np.float32)
+    lib().mrs_debug_staged_table(model.handle, max_contacts, which, out.ctypes.data if k else None, k)
+    return out
 
 
 RENDER_KERNELS = ["binned", "frame", "tile"]  # depth_kernel_mesh, depth_kernel_v2, depth_kernel
@@ -714,7 +753,8 @@ class Batch:
     def layout(self) -> dict:
         """kernel configuration of this batch (diagnostics): group width, LDS and scratch floats per
         env, blocked mode, pipe width, row and contact capacity, kinematic trees"""
-        keys = LAYOUT_KEYS + LAYOUT_OUTPUT_KEYS + LAYOUT_DYN_KEYS + LAYOUT_SOLVE_KEYS + LAYOUT_PAIR_KEYS
+        keys = (LAYOUT_KEYS + LAYOUT_OUTPUT_KEYS + LAYOUT_DYN_KEYS + LAYOUT_SOLVE_KEYS + LAYOUT_PAIR_KEYS +
+                LAYOUT_IMAGE_KEYS)
         out = np.zeros(len(keys), dtype=np.int32)
         k = lib().mrs_debug_batch_layout(self._h, out.ctypes.data, len(keys))
         return dict(zip(keys[:k], out[:k].tolist()))
